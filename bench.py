@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: adversarial images/sec, PGD-20, ViT-B/16 + LoRA r=8, batch 256 per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" is one pass of the hot path over one batch: a full PGD-20 attack
@@ -10,7 +10,12 @@ iteration one hipGraph launch) on 256 synthetic 224x224x3 images that are alread
 in HBM.  Image batches shard over ranks (weak scaling, no data-path collective; the frozen
 backbone and the adapters are replicated).  Rank 0 prints ONE JSON line.
 
-Extra objects in that line:
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line.
+--dump-outputs DIR writes what the last timed step returned (the adversarial images of rank 0) as
+DIR/adv.npy, float32; weights, images, labels and the random start of every step are seeded, so two
+runs with the same arguments attack the same inputs.
+
+Extra objects in that line, with --full only:
   roofline      the dominant kernel, timed live with HIP events on the launch stream
                 (vl_profile_begin/_report, include/vitlora.h) against the gfx950 dense fp16 / bf16
                 MFMA peak; plus `path` = whole-path algorithmic FLOP/s and `pgd_step` =
@@ -417,6 +422,27 @@ def self_launch(n):
     return rc
 
 
+DUMP_LIMIT_BYTES = 48 << 20
+
+
+def dump_outputs(path, adv):
+    """--dump-outputs: `adv` is what the last timed step returned to its caller (rank 0's adversarial images, [B, 3, S, S]).
+    Written whole as float32 when it fits DUMP_LIMIT_BYTES; otherwise the images of a fixed, seeded choice of batch indices
+    (sorted; the same choice for every run with the same batch), as many as fit."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = int(adv.shape[0])
+    keep = DUMP_LIMIT_BYTES // (4 * adv[0].numel())
+    if keep < 1:
+        raise SystemExit(f"[bench] --dump-outputs: one image of {4 * adv[0].numel()} bytes exceeds the limit")
+    if keep < n:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(1234))[:keep].sort().values
+        adv = adv[idx.to(adv.device)]
+    a = adv.detach().float().cpu().numpy()
+    np.save(os.path.join(path, "adv.npy"), a)
+    log(f"wrote {a.shape[0]} of {n} adversarial images to {os.path.join(path, 'adv.npy')} ({a.nbytes >> 20} MB, float32)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -426,9 +452,15 @@ def main():
     ap.add_argument("--pgd-steps", type=int, default=20)
     ap.add_argument("--rank", type=int, default=8, help="LoRA rank")
     ap.add_argument("--merged", action="store_true", help="fold LoRA into W (merge_and_unload) instead of fusing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned (rank 0's adversarial images; a seeded "
+                         "sample of whole images when the batch exceeds the size limit) to DIR/adv.npy as float32")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the secondary measurements: roofline pass, extras, CPU baseline "
+                         "(each can be switched off with its --no-... option)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
-    # BASELINE configs 5 and 4 are part of the default line since round 5 (the driver's run must witness them); --vitl / --swin
+    # BASELINE configs 5 and 4 are part of the --full line since round 5; --vitl / --swin
     # are still accepted (no-ops), --no-vitl / --no-swin skip them
     ap.add_argument("--vitl", action="store_true", default=True, help="extras: ViT-L/16 + LoRA r=16 at batch 128: PGD attack and patch EoT step (default on)")
     ap.add_argument("--no-vitl", dest="vitl", action="store_false")
@@ -441,6 +473,10 @@ def main():
     ap.add_argument("--precision", choices=("f16", "bf16", "f32"), default="f16",
                     help="f16: fp16 operands / fp32 accumulation (the MFMA-rate path); f32: the reference's own precision (parity mode)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:          # a plain run: the headline alone
+        args.no_roofline = args.no_extras = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -523,6 +559,8 @@ def main():
     value = imgs / dt
     if rank == 0:
         log(f"timed region: {dt:.3f} s for {args.steps} steps -> {value:.1f} img/s")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, adv)
     flops_img_step = algorithmic_flops_per_image_step(arch, args.rank, TARGETS)
 
     out = {

@@ -240,13 +240,13 @@ def test_two_rank_patch_attack_cli(tmp_path):
     assert (np.abs(p1 - p2) < 1e-6).mean() > 0.97
 
 
-def test_bench_contract_one_and_two_ranks():
+def test_bench_contract_one_and_two_ranks(tmp_path):
     """bench.py prints ONE JSON line with the driver's keys; under `torch.distributed.run` (two ranks sharing the GPU, gloo:
     BENCH_BACKEND / BENCH_SHARE_GPU) rank 0 alone prints it, n_gpus = 2 and the images of both ranks are counted."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    small = ["--steps", "1", "--warmup", "1", "--batch", "32", "--pgd-steps", "2", "--no-cpu-baseline", "--no-extras"]
+    small = ["--full", "--steps", "1", "--warmup", "1", "--batch", "32", "--pgd-steps", "2", "--no-cpu-baseline", "--no-extras"]
     env = dict(os.environ, BENCH_BACKEND="gloo", BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1")
     lines = {}
     # n = 1; n = 2 under the driver's launcher; "self": plain `python bench.py --gpus 2`, which starts its own two ranks
@@ -257,16 +257,23 @@ def test_bench_contract_one_and_two_ranks():
         e = dict(env)
         if tag == "self":
             e.pop("WORLD_SIZE", None)
-        r = subprocess.run(launcher + [os.path.join(root, "bench.py"), "--gpus", str(n)] + small, env=e, capture_output=True,
+        dump = ["--dump-outputs", str(tmp_path / "dump")] if tag == 1 else []
+        r = subprocess.run(launcher + [os.path.join(root, "bench.py"), "--gpus", str(n)] + small + dump, env=e, capture_output=True,
                            text=True, timeout=600)
         assert r.returncode == 0, (tag, r.stderr[-1500:])
         js = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
         assert len(js) == 1, r.stdout[-500:]
         lines[tag] = json.loads(js[0])
+    # --dump-outputs: the adversarial images the last timed attack returned, float32: the seeded input batch moved by at most
+    # eps per pixel, inside [0, 1], and moved somewhere
+    adv = np.load(tmp_path / "dump" / "adv.npy")
+    x0 = importlib.import_module(PKG + ".synthetic").random_batch(pkg().ArchConfig(num_labels=21), 32, seed=100)[0].numpy()
+    assert adv.dtype == np.float32 and adv.shape == x0.shape == (32, 3, 224, 224)
+    assert np.abs(adv - x0).max() <= 8 / 255 + 1e-6 and adv.min() >= 0.0 and adv.max() <= 1.0 and np.abs(adv - x0).mean() > 1e-3
     # what north_star names at N > 1: strong scaling (the GLOBAL batch split into contiguous shards) and BASELINE
     # config 3's data-parallel step -- PGD-7 + LoRA train step on every rank WITH the flat-gradient all-reduce
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", free_port(), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
+                        "--master-port", free_port(), os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--steps", "1", "--warmup", "1",
                         "--batch", "32", "--pgd-steps", "2", "--no-cpu-baseline", "--no-roofline", "--scaling", "strong"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-1500:]

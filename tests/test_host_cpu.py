@@ -309,6 +309,29 @@ def test_integration_md_indexes_every_abi_symbol():
     assert listed - syms == set(), sorted(listed - syms)
 
 
+def test_bench_dump_outputs_is_float32_bounded_and_repeatable(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (host side, no GPU): a small output is written whole; one above the limit as whole images of a
+    seeded, sorted choice of batch indices that is the same on every call; always float32 and never above 64 MB."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    small = torch.rand(5, 3, 16, 16, generator=torch.Generator().manual_seed(0)).half()
+    bench.dump_outputs(str(tmp_path / "s"), small)
+    a = np.load(tmp_path / "s" / "adv.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, small.float().numpy())
+    assert bench.DUMP_LIMIT_BYTES <= 64 << 20
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1 << 16)  # the same rule at a size that costs nothing
+    per = bench.DUMP_LIMIT_BYTES // 4 // 8                    # 8 images fit exactly, 19 do not
+    big = torch.arange(19, dtype=torch.float32)[:, None].expand(19, per).contiguous()       # image i holds the value i
+    bench.dump_outputs(str(tmp_path / "b1"), big)
+    bench.dump_outputs(str(tmp_path / "b2"), big)
+    b1, b2 = np.load(tmp_path / "b1" / "adv.npy"), np.load(tmp_path / "b2" / "adv.npy")
+    assert b1.dtype == np.float32 and b1.shape == (8, per) and b1.nbytes <= bench.DUMP_LIMIT_BYTES
+    assert np.array_equal(b1, b2)
+    ids = b1[:, 0]
+    assert (b1 == ids[:, None]).all() and (np.diff(ids) > 0).all() and set(ids) <= set(range(19))
+
+
 def test_adam_drop_last_step_and_bench_flop_accounting():
     """Host logic added in round 5 (no GPU): (i) `optim.Adam.drop_last_step` takes a dropped optimizer step out of the
     bias-correction count, as an AMP skip-step never calls `optimizer.step()` (train_loras.py:314; round-4 ADVICE); (ii) the

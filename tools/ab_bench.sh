@@ -1,16 +1,19 @@
 #!/bin/bash
 # A/B on one GPU box: working-tree library (B) against csrc/build/libA.so (A), alternating runs.
-# usage (inside gpurun): tools/ab_bench.sh [pairs]     -> gpurun_out/ab_{A,B}{i}.log
+# usage (from the repository root): tools/ab_bench.sh [pairs]     -> $AB_OUT/ab_{A,B}{i}.log (AB_OUT defaults to ab_out)
 P=adapting-pretrained-vision-transformers-with-lora-against-attack-vectors_amd
 A=$PWD/$P/csrc/build/libA.so
 N=${1:-2}
+export AB_OUT=${AB_OUT:-ab_out}
+mkdir -p $AB_OUT
+B="python bench.py --full --steps 1 --warmup 1 --pgd-steps 4 --no-cpu-baseline --no-extras"
 for i in $(seq 1 $N); do
-  timeout -k 10 200 python bench.py --steps 1 --warmup 1 --pgd-steps 4 --no-cpu-baseline --no-extras > gpurun_out/ab_B$i.log 2>/dev/null || exit 1
-  VITLORA_LIB=$A timeout -k 10 200 python bench.py --steps 1 --warmup 1 --pgd-steps 4 --no-cpu-baseline --no-extras > gpurun_out/ab_A$i.log 2>/dev/null || exit 1
+  timeout -k 10 200 $B > $AB_OUT/ab_B$i.log 2>/dev/null || exit 1
+  VITLORA_LIB=$A timeout -k 10 200 $B > $AB_OUT/ab_A$i.log 2>/dev/null || exit 1
 done
 python - <<'PY'
-import json, glob
-for f in sorted(glob.glob("gpurun_out/ab_[AB]*.log")):
+import json, glob, os
+for f in sorted(glob.glob(os.path.join(os.environ["AB_OUT"], "ab_[AB]*.log"))):
     d = json.loads(open(f).read())
     k = d["roofline"]["kernels_ms_per_pgd_iteration"]
     g = sum(v for n, v in k.items() if n.startswith("gemm256"))

@@ -3,7 +3,7 @@
 P=adapting-pretrained-vision-transformers-with-lora-against-attack-vectors_amd
 A=$PWD/$P/csrc/build/libA.so
 N=${1:-2}
-B="python bench.py --precision bf16 --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
+B="python bench.py --full --precision bf16 --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
 for i in $(seq 1 $N); do
   timeout -k 10 200 $B > gpurun_out/abbf_B$i.json 2>/dev/null || exit 1
   VITLORA_LIB=$A timeout -k 10 200 $B > gpurun_out/abbf_A$i.json 2>/dev/null || exit 1

@@ -2,7 +2,7 @@
 # same-box A/B of an environment switch: tools/ab_env.sh "VAR=value" [pairs]   (inside gpurun; prints img/s and the kernel table diff)
 set -e
 SW="$1"; N=${2:-2}
-B="python bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-extras"
+B="python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-extras"
 for i in $(seq 1 $N); do
   timeout -k 10 200 $B > gpurun_out/abenv_A$i.json 2> /dev/null
   env $SW timeout -k 10 200 $B > gpurun_out/abenv_B$i.json 2> /dev/null

@@ -3,7 +3,7 @@
 # prints img/s and every kernel line >= 0.15 ms of the kernel table per run; the working-tree library is arm "cur"
 P=adapting-pretrained-vision-transformers-with-lora-against-attack-vectors_amd
 N=$1; shift
-B="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras"
+B="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras"
 rm -f gpurun_out/abl_*.json
 for i in $(seq 1 $N); do
   timeout -k 10 200 $B > gpurun_out/abl_cur_$i.json 2>/dev/null || exit 1

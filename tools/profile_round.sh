@@ -10,7 +10,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd $ROOT
 export TMPDIR=/tmp
-BENCH="python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extras"
+BENCH="python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-extras"
 PMCB="python3 bench.py --steps 1 --warmup 0 --pgd-steps 2 --no-cpu-baseline --no-roofline --no-extras"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ktrace -- $BENCH > $OUT/bench_under_rocprof.json 2> $OUT/ktrace.log
 cp $(find $OUT/ktrace -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv
