@@ -18,6 +18,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "env.h"
 #include "kernels.h"
 #include "prof.h"
 
@@ -1483,7 +1484,7 @@ int attention32_init(int device) {
     if (e != hipSuccess) return (int)e;
     e = hipFuncSetAttribute((const void*)attn_bwd_ring_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bwd_ring_lds<7>());
     if (e != hipSuccess) return (int)e;
-    if (const char* rg = getenv("VITLORA_ATTN_RING")) g_attn_ring = rg[0] != '0';
+    g_attn_ring = env_flag("VITLORA_ATTN_RING", g_attn_ring != 0);
     done[device] = true;
     return 0;
 }

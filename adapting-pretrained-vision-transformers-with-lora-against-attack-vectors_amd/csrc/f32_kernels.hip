@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "env.h"
 #include "f32_kernels.h"
 #include "prof.h"
 
@@ -784,7 +785,7 @@ int g_f32_big = 1;       // VITLORA_F32_BIG=0: every fp32 GEMM on the 64 x 64 ti
 int g_f32_attn_mfma = 1; // VITLORA_F32_ATTN=0: the scalar fp32 attention kernels (A/B)
 
 int f32_init(int device) {
-    if (const char* e = getenv("VITLORA_F32_BIG")) g_f32_big = e[0] != '0';
+    g_f32_big = env_flag("VITLORA_F32_BIG", g_f32_big != 0);
     static bool done[64] = {};
     if (device < 0 || device >= 64) return -1;
     if (done[device]) return 0;
@@ -797,7 +798,7 @@ int f32_init(int device) {
     if (e != hipSuccess) return (int)e;
     e = hipFuncSetAttribute((const void*)attn_bwd_f32_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_mfma_lds_bytes(ATMAX));
     if (e != hipSuccess) return (int)e;
-    if (const char* a = getenv("VITLORA_F32_ATTN")) g_f32_attn_mfma = a[0] != '0';
+    g_f32_attn_mfma = env_flag("VITLORA_F32_ATTN", g_f32_attn_mfma != 0);
     done[device] = true;
     return 0;
 }

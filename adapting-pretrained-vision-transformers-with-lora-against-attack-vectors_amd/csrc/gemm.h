@@ -53,7 +53,7 @@ struct GemmArgs {
     int no_pp;        // 1: never the ping-pong kernel (the Swin stages 3-4 shapes -- M = 50 176 / 12 544 rows, N = 512 .. 3 072 -- run 1.5 % of a step
                       // faster on the 256-row kernel: 17.30 vs 17.56 ms, same box, round 5)
     int tile_group;   // gemm256: tile rows per group of the tile walk (0 = 8 for N >= 2048, else 1; 1 = row-major, the round-1 order)
-    int dephase;      // gemm256: start offset unit (x 8128 cycles x (workgroup/8 mod 4)); 0 = off
+    int dephase;      // gemm256: start offset unit (x 8128 cycles x (workgroup/8 mod 4)); always 0 -- no host code sets it, kept with its branch because gemm256's register allocation changes without them
     // EPI_DROP_ACC: dropout mask of element (m, n) of the module input = drop_scale(seed, stream, m*N + n)
     const h16* G; int ldg;          // optional extra factor (gelu'(z) for the fc2 input gradient)
     uint64_t drop_seed; uint32_t drop_stream; float drop_p, drop_inv_keep;

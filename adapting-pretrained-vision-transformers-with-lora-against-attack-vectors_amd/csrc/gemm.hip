@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "env.h"
 #include "gemm_epi.h"
 #include "prof.h"
 
@@ -173,7 +174,6 @@ void set_attr() {
 }
 
 int g_force_small = -1;
-int g_dephase = -1;
 int g_tile_group = -1;
 int g_skinny_bm = 128;      // VITLORA_SKINNY_BM=64: 64-row tiles (4 LDS stages) for the skinny LoRA-down GEMM
 
@@ -200,12 +200,9 @@ int gemm_init(int device) {
     if (int e2 = gemm256_init()) g_attr_err = e2;
     if (int e3 = gemm_pp_init()) g_attr_err = e3;
     if (int e4 = gemm_stream_init()) g_attr_err = e4;
-    const char* e = getenv("VITLORA_GEMM128");      // A/B switch: force the 128-row kernel
-    g_force_small = (e && e[0] == '1') ? 1 : 0;
-    const char* dp = getenv("VITLORA_DEPHASE");      // experiment knob: start-offset unit of gemm256
-    if (dp) g_dephase = atoi(dp);
-    if (const char* tg = getenv("VITLORA_TILE_GROUP")) g_tile_group = atoi(tg);
-    if (const char* sb = getenv("VITLORA_SKINNY_BM")) g_skinny_bm = atoi(sb);     // experiment knob: gemm256 tile walk
+    g_force_small = env_flag("VITLORA_GEMM128", false) ? 1 : 0;      // A/B switch: force the 128-row kernel
+    g_tile_group = env_int("VITLORA_TILE_GROUP", g_tile_group);      // experiment knob: gemm256 tile walk
+    g_skinny_bm = env_int("VITLORA_SKINNY_BM", g_skinny_bm);
     if (g_attr_err) return g_attr_err;
     done[device] = true;
     return 0;
@@ -229,7 +226,6 @@ void launch_gemm(const GemmArgs& a, int epi, int bn, hipStream_t s) {
     }
     if (bn != 64 && g_force_small != 1 && !narrow && gemm256_supports(a, epi)) {
         GemmArgs b = a;
-        if (g_dephase >= 0) b.dephase = g_dephase;
         if (g_tile_group >= 0) b.tile_group = g_tile_group;
         launch_gemm256(b, epi, s);
         return;

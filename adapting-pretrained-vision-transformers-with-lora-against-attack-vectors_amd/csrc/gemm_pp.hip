@@ -32,6 +32,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "env.h"
 #include "gemm_epi.h"
 #include "prof.h"
 
@@ -474,7 +475,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmArgs p, int ntil
 int g_pp_cus = 0;
 int g_pp_mode = 2;          // VITLORA_GEMM_PP: 0 = off, 1 = every supported GEMM, 2 = the shapes it wins on (plain 16-bit stores, K <= 2304)
 int g_pp_attr_err = 0;
-int g_pp_max_k = 2304;      // VITLORA_GEMM_PP_MAXK: deepest plain-store product sent here in mode 2
+constexpr int g_pp_max_k = 2304;      // deepest plain-store product sent here in mode 2
 
 template <int EPI, int ND, bool BC = false>
 void launch_pp(const GemmArgs& a, hipStream_t s) {
@@ -533,8 +534,7 @@ bool gemm_pp_supports(const GemmArgs& a, int epi) {
 
 int gemm_pp_init() {
     g_pp_attr_err = 0;
-    if (const char* e = getenv("VITLORA_GEMM_PP")) g_pp_mode = atoi(e);
-    if (const char* e = getenv("VITLORA_GEMM_PP_MAXK")) g_pp_max_k = atoi(e);
+    g_pp_mode = env_int("VITLORA_GEMM_PP", g_pp_mode);
     int dev = 0;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) g_pp_cus = prop.multiProcessorCount;

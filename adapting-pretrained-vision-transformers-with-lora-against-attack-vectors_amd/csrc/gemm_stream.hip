@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "env.h"
 #include "gemm_epi.h"
 #include "prof.h"
 
@@ -340,11 +341,11 @@ int gemm_stream_init() {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
     g_stream_cus = cus;
-    if (const char* e = getenv("VITLORA_GEMM_STREAM")) g_stream_on = e[0] != '0';
-    if (const char* e = getenv("VITLORA_GEMM_STREAM_MIN_ROWS")) g_stream_min_rows = atoi(e);
-    if (const char* e = getenv("VITLORA_GEMM_STREAM_MIN_ROWS64")) g_stream_min_rows64 = atoi(e);
-    if (const char* e = getenv("VITLORA_GEMM_STREAM_MAX_K")) g_stream_max_k = atoi(e);
-    if (const char* e = getenv("VITLORA_GEMM_STREAM_DOWN")) g_stream_down = e[0] != '0';
+    g_stream_on = env_flag("VITLORA_GEMM_STREAM", g_stream_on != 0);
+    g_stream_min_rows = env_int("VITLORA_GEMM_STREAM_MIN_ROWS", g_stream_min_rows);
+    g_stream_min_rows64 = env_int("VITLORA_GEMM_STREAM_MIN_ROWS64", g_stream_min_rows64);
+    g_stream_max_k = env_int("VITLORA_GEMM_STREAM_MAX_K", g_stream_max_k);
+    g_stream_down = env_flag("VITLORA_GEMM_STREAM_DOWN", g_stream_down != 0);
     return g_stream_err;
 }
 

@@ -20,8 +20,8 @@
 #include "../../include/vitlora.h"
 #include "f32_kernels.h"
 #include "kernels.h"
+#include "env.h"
 #include "model.h"
-#include "mlp_fused.h"
 #include "prof.h"
 
 namespace VLNS {      // vl_f16 / vl_bf16: the 16-bit path is compiled once per operand type (common.h)
@@ -1112,23 +1112,15 @@ struct vl_swin {
     h16 *xlast16 = nullptr, *hfin16 = nullptr, *dhfin16 = nullptr;      // 16-bit path: last stage's output stream, final LayerNorm output, its gradient
     int f16 = 0;             // cfg.reserved[0] == 1: 16-bit operand path for the blocks (embedding, merging and head stay fp32)
     int dirty = 1;           // packed h16 operands are stale (weights / adapters written since the last commit)
-    int fuse_merge = 1;      // VITLORA_SWIN_FUSE_MERGE=0: separate materialise / gather / LayerNorm / pack passes around the merges
     // vl_swin_pgd_attack as TWO half-batch chains on two streams (round 5; the ViT path got them in round 4): stages 3-4 are
     // small-batch shaped at any batch (M = 50 176 / 12 544 rows: 392 / 147 tiles on 256 CUs) and the window kernels run one or two waves
     // per SIMD, so the ends of one chain's kernels meet the main loops of the other's.  The chains are shallow copies of the handle
     // (shared weights) whose workspace pointers are carved into the SAME planned bytes as the main workspace (never live together).
     static constexpr int MAXCH = 4;
     vl_swin* chain[MAXCH] = {nullptr, nullptr, nullptr, nullptr};
-    int chain_offset = 0;
     int chain_batch = 0, chains_on = 2, chain_min = 32;      // VITLORA_SWIN_CHAINS = number of chains (0 / 1: off, default 2, at most 4); VITLORA_SWIN_CHAIN_MIN: smallest batch that is split
     hipStream_t side[MAXCH - 1] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int mlp_fused = 0;       // VITLORA_SWIN_MLP_FUSED=1: stage 1's MLP (fc1 -> GELU -> fc2, and its backward) in ONE kernel with the hidden activation in
-                             // LDS (csrc/mlp_fused.hip).  Built, tested and measured in round 5 and NOT the default: it removes 2.0 GB of HBM traffic per
-                             // block and is SLOWER (660 + 533 us against 491 + 462 us for the two-launch forms at batch 256): these products are bound
-                             // by the erf-GELU VALU work (308 M elements x ~25 instructions = 0.21 ms per launch) and by per-step synchronisation, not by
-                             // their bytes -- profiles/r05_swin_mlp_fused.txt
-    int pp_down = 0;         // VITLORA_SWIN_PP_DOWN=1: stages 3-4 compute the o / fc2 LoRA down projections inside the ping-pong GEMM instead of as separate skinny GEMMs (round 5: built, bit-compatible, time-neutral -- 18.38 / 18.47 vs 18.42 / 18.28 ms per step, alternating on one box -- so the simpler form stays)
     int unpad_stages = 3;    // bit i: stage i keeps its h16 activations at their true width (VITLORA_SWIN_UNPAD; default since round 5: stages 1 and 2, C = 96 / 192 -- every h16 activation is then dense, there are no pad columns at all; stage 2 alone is time-neutral)
 };
 
@@ -1227,16 +1219,14 @@ void swin16_commit(vl_swin* m, hipStream_t s) {
 // y = x W^T + b (+ LoRA as one extra K tile), epilogue `epi`; x [Mp][inP] h16
 void lin16_fwd(vl_swin* m, SStage& st, const SLin& ln, const h16* x, int ldx, int Mp, int M, GemmArgs g, int epi, hipStream_t s) {
     g.A1 = x; g.lda1 = ldx; g.W1 = ln.W16; g.ldw1 = ln.inP; g.K1 = ln.inP;
-    g.M = Mp; g.Mvalid = M; g.N = ln.outN; g.bias = ln.b16; g.no_pp = m->pp_down ? 0 : 1;
+    g.M = Mp; g.Mvalid = M; g.N = ln.outN; g.bias = ln.b16; g.no_pp = 1;
     g.n_store = g.ldc < ln.outN ? ln.out : 0;                      // unpadded result rows (ldc = out)
     if (ln.kext) {
         g.W2 = ln.Bu; g.ldw2 = 64; g.K2 = 64;
         g.k2_algo = m->r; g.k2_used = m->r * (int)ln.slots.size();
         g.down_W = ln.Ad; g.down_ldw = ln.inP; g.down_groups = 1;
-        // the down projection rides inside the GEMM where a kernel can carry it: the streaming kernel (stages 1-2) or, for ONE
-        // adapted module of r <= 16 (o, fc2), the ping-pong kernel's helper group (stages 3-4, round 5)
-        const bool pp_down = m->pp_down && ln.slots.size() == 1 && m->r <= 16 && g.ldc >= ln.outN && gemm_pp_fuses_down(g, epi);
-        if (!gemm_stream_fuses_down(g, epi) && !pp_down) {          // t = x Ad^T as its own skinny GEMM, read back as the LoRA K tile's A operand
+        // the down projection rides inside the GEMM where a kernel can carry it: the streaming kernel (stages 1-2)
+        if (!gemm_stream_fuses_down(g, epi)) {          // t = x Ad^T as its own skinny GEMM, read back as the LoRA K tile's A operand
             g.down_W = nullptr; g.down_ldw = 0; g.down_groups = 0;
             GemmArgs d = ga(x, ldx, ln.Ad, ln.inP, ln.inP, Mp, 64);
             d.Mvalid = M; d.C = st.t16; d.ldc = 64; d.n_algo = m->r * (int)ln.slots.size();
@@ -1249,14 +1239,13 @@ void lin16_fwd(vl_swin* m, SStage& st, const SLin& ln, const h16* x, int ldx, in
 // dx = dy W (+ LoRA), dy [Mp][outP] h16
 void lin16_dgrad(vl_swin* m, SStage& st, const SLin& ln, const h16* dy, int ldy, int Mp, int M, GemmArgs g, int epi, hipStream_t s) {
     g.A1 = dy; g.lda1 = ldy; g.W1 = ln.WT16; g.ldw1 = ln.outP; g.K1 = ln.outP;
-    g.M = Mp; g.Mvalid = M; g.N = ln.inN; g.bias = nullptr; g.no_pp = m->pp_down ? 0 : 1;
+    g.M = Mp; g.Mvalid = M; g.N = ln.inN; g.bias = nullptr; g.no_pp = 1;
     g.n_store = g.ldc < ln.inN ? ln.in : 0;
     if (ln.kext) {
         g.W2 = ln.Au; g.ldw2 = 64; g.K2 = 64;
         g.k2_algo = m->r * (int)ln.slots.size(); g.k2_used = g.k2_algo;
         g.down_W = ln.Bd; g.down_ldw = ln.outP; g.down_groups = 1;
-        const bool pp_down = m->pp_down && ln.slots.size() == 1 && m->r <= 16 && g.ldc >= ln.inN && gemm_pp_fuses_down(g, epi);
-        if (!gemm_stream_fuses_down(g, epi) && !pp_down) {
+        if (!gemm_stream_fuses_down(g, epi)) {
             g.down_W = nullptr; g.down_ldw = 0; g.down_groups = 0;
             GemmArgs d = ga(dy, ldy, ln.Bd, ln.outP, ln.outP, Mp, 64);
             d.Mvalid = M; d.C = st.u16; d.ldc = 64; d.n_algo = m->r;
@@ -1265,30 +1254,6 @@ void lin16_dgrad(vl_swin* m, SStage& st, const SLin& ln, const h16* dy, int ldy,
         }
     }
     launch_gemm(g, epi, 128, s);
-}
-
-// Arguments of the fused MLP kernel (csrc/mlp_fused.hip) for this block, forward or backward; false when the block's shapes or
-// adapters are outside what it covers (then the two GEMM launches run): C <= 128 -- Swin-T stage 1 --, at most fc2 adapted
-// (one module, r <= 16), unpadded 16-bit activations.
-bool mlp_args(vl_swin* m, SStage& st, SBlock& bk, int Mp, int M, bool backward, MlpArgs* out) {
-    if (!m->mlp_fused || bk.fc1.kext || bk.fc2.slots.size() > 1 || (bk.fc2.kext && m->r > 16)) return false;
-    if (bk.fc2.outN != 128 || bk.fc1.inN != 128 || st.LD != st.C || st.L4 != 4 * st.C) return false;
-    MlpArgs a;
-    memset(&a, 0, sizeof a);
-    a.M = Mp; a.Mvalid = M; a.HID = bk.fc1.outN; a.S = bk.z16; a.lds_ = st.L4; a.n_store = st.C; a.K1_algo = st.C;
-    a.lora = bk.fc2.kext ? 1 : 0; a.r_algo = m->r;
-    if (!backward) {
-        a.X = st.h16b; a.ldx = st.LC; a.K1 = bk.fc1.inP; a.Wa = bk.fc1.W16; a.ldwa = bk.fc1.inP; a.bias1 = bk.fc1.b16;
-        a.Wb = bk.fc2.W16; a.ldwb = bk.fc2.inP; a.bias2 = bk.fc2.b16; a.Y = st.delta16; a.ldy = st.LD;
-        a.Ldown = bk.fc2.Ad; a.ldd = bk.fc2.inP; a.Lup = bk.fc2.Bu;
-    } else {
-        a.X = st.gh16; a.ldx = st.LC; a.K1 = bk.fc2.outP; a.Wa = bk.fc2.WT16; a.ldwa = bk.fc2.outP;
-        a.Wb = bk.fc1.WT16; a.ldwb = bk.fc1.outP; a.Y = st.dh16; a.ldy = st.LD;
-        a.Ldown = bk.fc2.Bd; a.ldd = bk.fc2.outP; a.Lup = bk.fc2.Au;
-    }
-    if (bk.fc1.outN != bk.fc2.inN || bk.fc1.outP != bk.fc1.outN || !mlp_fused_supports(a)) return false;
-    *out = a;
-    return true;
 }
 
 // One Swin block, forward, on the 16-bit residual stream (round 5).  x_prev16: the stream entering the PREVIOUS block's MLP
@@ -1311,11 +1276,6 @@ void swin16_block_fwd(vl_swin* m, SStage& st, SBlock& bk, const h16* x_prev16, b
     lin16_fwd(m, st, bk.o, st.ctx16, st.LC, Mp, M, g, EPI_STORE_H16, s);
     // LayerNorm 2 (+ residual add of the attention output: xa16 + delta -> xb16)
     sw_ln_fwd16<false>(bk.xa16, Cs, st.delta16, st.LD, bk.xb16, Cs, st.h16b, st.LC, bk.mean2, bk.rstd2, bk.ln2_g, bk.ln2_b, M, Cs, m->cfg.ln_eps, m->err_flag, s);
-    MlpArgs ma;
-    if (mlp_args(m, st, bk, Mp, M, false, &ma)) {       // narrow stage: fc1 -> GELU -> fc2 in ONE kernel, the hidden activation stays in LDS
-        launch_mlp_fused(ma, 0, s);
-        return;
-    }
     memset(&g, 0, sizeof g); g.C = st.a16; g.ldc = st.L4; g.C2 = bk.z16; g.ldc2 = st.L4;
     lin16_fwd(m, st, bk.fc1, st.h16b, st.LC, Mp, M, g, EPI_GELU, s);
     memset(&g, 0, sizeof g); g.C = st.delta16; g.ldc = st.LD;
@@ -1328,14 +1288,10 @@ void swin16_block_bwd(vl_swin* m, SStage& st, SBlock& bk, int B, int shift, hipS
     const int Cs = st.C, Hs = st.H, M = B * Hs * Hs, Mp = (int)round_up(M, 128);
     const int nW = (Hs / WS) * (Hs / WS);
     GemmArgs g;
-    MlpArgs ma;
-    if (mlp_args(m, st, bk, Mp, M, true, &ma)) launch_mlp_fused(ma, 1, s);       // fc2 dgrad -> * gelu'(z) -> fc1 dgrad in one kernel
-    else {
     memset(&g, 0, sizeof g); g.C = st.dz16; g.ldc = st.L4; g.R = bk.z16; g.ldr = st.L4;
     lin16_dgrad(m, st, bk.fc2, st.gh16, st.LC, Mp, M, g, EPI_GELU_BWD, s);                         // d(z) = (d(out) Wfc2) * gelu'(z)
     memset(&g, 0, sizeof g); g.C = st.dh16; g.ldc = st.LD;
     lin16_dgrad(m, st, bk.fc1, st.dz16, st.L4, Mp, M, g, EPI_STORE_H16, s);
-    }
     sw_ln_bwd16<false, false>(st.dh16, st.LD, bk.xb16, Cs, bk.mean2, bk.rstd2, bk.ln2_g, st.gh16, st.gh16, st.LC, M, Cs, m->err_flag, s);
     memset(&g, 0, sizeof g); g.C = st.dctx16; g.ldc = st.LD;
     lin16_dgrad(m, st, bk.o, st.gh16, st.LC, Mp, M, g, EPI_STORE_H16, s);
@@ -1381,22 +1337,16 @@ int vl_swin_create(const vl_swin_config* cfg, vl_swin** out) {
     HIPCHK(hipGetDevice(&dev));
     if (int e = f32_init(dev)) return vl_fail(VL_ERR_HIP, "f32_init failed (%d)", e);
     if (cfg->reserved[0] != 0 && cfg->reserved[0] != 1) return vl_fail(VL_ERR_ARG, "precision (reserved[0]) must be 0 (f32) or 1 (f16)");
-    if (cfg->reserved[0] == 1) {
+    if (cfg->reserved[0] == 1)
         if (int e = gemm_init(dev)) return vl_fail(VL_ERR_HIP, "gemm_init: hipFuncSetAttribute failed (%d)", e);
-        if (int e = mlp_fused_init()) return vl_fail(VL_ERR_HIP, "mlp_fused_init: hipFuncSetAttribute failed (%d)", e);
-    }
     vl_swin* m = new vl_swin();
     m->cfg = *cfg;
     m->f16 = cfg->reserved[0] == 1;
-    if (const char* up = getenv("VITLORA_SWIN_UNPAD")) m->unpad_stages = atoi(up);
-    if (const char* pd = getenv("VITLORA_SWIN_PP_DOWN")) m->pp_down = atoi(pd);
-    if (const char* mf = getenv("VITLORA_SWIN_MLP_FUSED")) m->mlp_fused = atoi(mf);
-    if (const char* ch = getenv("VITLORA_SWIN_CHAINS")) m->chains_on = std::min(atoi(ch), (int)vl_swin::MAXCH);
-    if (const char* cm = getenv("VITLORA_SWIN_CHAIN_MIN")) m->chain_min = atoi(cm);
-    if (const char* co = getenv("VITLORA_SWIN_CHAIN_OFFSET")) m->chain_offset = atoi(co);
-    if (const char* wc = getenv("VITLORA_SWIN_WIN_CUS")) g_win_cus = atoi(wc);
-    if (const char* wb = getenv("VITLORA_SWIN_WIN_BWD")) g_win_bwd_per_cu = atoi(wb);
-    if (const char* fm = getenv("VITLORA_SWIN_FUSE_MERGE")) m->fuse_merge = fm[0] != '0';
+    m->unpad_stages = env_int("VITLORA_SWIN_UNPAD", m->unpad_stages);
+    m->chains_on = std::min(env_int("VITLORA_SWIN_CHAINS", m->chains_on), (int)vl_swin::MAXCH);
+    m->chain_min = env_int("VITLORA_SWIN_CHAIN_MIN", m->chain_min);
+    g_win_cus = env_int("VITLORA_SWIN_WIN_CUS", g_win_cus);
+    g_win_bwd_per_cu = env_int("VITLORA_SWIN_WIN_BWD", g_win_bwd_per_cu);
     m->S = cfg->image_size; m->P = cfg->patch_size; m->G0 = m->S / m->P; m->E = cfg->embed_dim; m->C = cfg->num_labels;
     m->r = cfg->lora_targets ? cfg->lora_r : 0;
     m->scaling = m->r ? cfg->lora_alpha / (float)m->r : 0.f;
@@ -1405,7 +1355,7 @@ int vl_swin_create(const vl_swin_config* cfg, vl_swin** out) {
     const int PK = 3 * m->P * m->P;
     A_(m->Wpe, (size_t)m->E * PK); A_(m->bpe, m->E); A_(m->eg, m->E); A_(m->eb, m->E);
     m->pe16 = m->f16 && m->P == 4 && m->E <= 128 && m->E % 32 == 0;
-    if (const char* pe = getenv("VITLORA_SWIN_PE16")) m->pe16 = m->pe16 && atoi(pe) != 0;
+    m->pe16 = m->pe16 && env_int("VITLORA_SWIN_PE16", 1) != 0;
     if (m->pe16) { A_(m->Wpe16, (size_t)128 * 64); A_(m->WpeT16, (size_t)128 * 128); A_(m->bpe16, 128); }
     // flat LoRA buffer layout: [stage][block][target q,k,v,o,fc1,fc2]{A, B}
     int64_t off = 0;
@@ -1999,23 +1949,14 @@ int vl_swin_pgd_attack(vl_swin* m, const float* x0, const int64_t* labels, int b
         else if (adv_out != x0) HIPCHK(hipMemcpyAsync(adv_out, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
         for (int c = 0; c < NC; ++c)
             HIPCHK(hipMemcpyAsync(m->chain[c]->stage_adv, adv_out + first[c] * img, (size_t)bsz[c] * img * sizeof(float), hipMemcpyDeviceToDevice, s));
-        // chain_offset: the other chains start when chain 0 has finished its FIRST forward, so that from then on one chain is in the
-        // MFMA / latency-bound half of a step while the other is in the VALU / HBM-bound half (VITLORA_SWIN_CHAIN_OFFSET)
-        const bool offset = m->chain_offset != 0;
-        if (!offset) {
-            HIPCHK(hipEventRecord(m->ev_fork, s));
-            for (int c = 1; c < NC; ++c) HIPCHK(hipStreamWaitEvent(m->side[c - 1], m->ev_fork, 0));
-        }
+        HIPCHK(hipEventRecord(m->ev_fork, s));
+        for (int c = 1; c < NC; ++c) HIPCHK(hipStreamWaitEvent(m->side[c - 1], m->ev_fork, 0));
         for (int i = 0; i < steps; ++i)
             for (int c = 0; c < NC; ++c) {
                 vl_swin* ch = m->chain[c];
                 hipStream_t sc = c ? m->side[c - 1] : s;
                 const int64_t nc = (int64_t)bsz[c] * img;
                 if ((rc = swin_forward(ch, ch->stage_adv, bsz[c], 1, sc))) return rc;
-                if (offset && i == 0 && c == 0) {
-                    HIPCHK(hipEventRecord(m->ev_fork, s));
-                    for (int k = 1; k < NC; ++k) HIPCHK(hipStreamWaitEvent(m->side[k - 1], m->ev_fork, 0));
-                }
                 k_ce_loss(ch->logits, ch->stage_labels, bsz[c], ch->C, ch->dlogits, ch->loss_img, ch->loss, ch->err_flag, sc);
                 ch->have_loss = 1;
                 if ((rc = swin_backward(ch, ch->grad_img, sc))) return rc;

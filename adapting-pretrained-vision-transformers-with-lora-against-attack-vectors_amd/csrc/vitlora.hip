@@ -11,7 +11,8 @@
 #include <vector>
 
 #include "common.h"
-#include "api_rename.h"      // handle-taking entry points are declared and defined as vl_*_f16 / vl_*_bf16 (api_dispatch.cpp exports the ABI names)
+#include "env.h"
+#include "api_rename.h"     // handle-taking entry points are declared and defined as vl_*_f16 / vl_*_bf16 (api_dispatch.cpp exports the ABI names)
 #include "model.h"
 #include "prof.h"
 
@@ -254,6 +255,14 @@ bool capturing(hipStream_t s) {
     return st != hipStreamCaptureStatusNone;
 }
 
+// the three switches that are neither a flag nor an integer (every other one goes through env.h)
+// VITLORA_RESID: "ln" = 0, "o" = 1, anything else or unset = 2 (vl_model::resid_epi)
+int env_resid() { const char* e = getenv("VITLORA_RESID"); return !e ? 2 : !strcmp(e, "ln") ? 0 : !strcmp(e, "o") ? 1 : 2; }
+// VITLORA_ATTN_IMG: unset = -1 (by batch size), a value starting with '1' = on, any other value = off
+int env_attn_img() { const char* e = getenv("VITLORA_ATTN_IMG"); return e ? (e[0] == '1' ? 1 : 0) : -1; }
+// VITLORA_GRAPH_DUMP: a file path, nullptr when unset or empty
+const char* env_graph_dump() { const char* e = getenv("VITLORA_GRAPH_DUMP"); return e && e[0] ? e : nullptr; }
+
 }  // namespace
 
 bool vl_drop_on(const vl_model* m) { return m->cur_train && m->r && m->cfg.lora_dropout > 0.f; }
@@ -304,8 +313,7 @@ int vl_create(const vl_config* cfg, vl_model** out) {
     m->C = cfg->num_labels; m->PK = 3 * cfg->patch_size * cfg->patch_size;
     m->r = cfg->lora_targets ? cfg->lora_r : 0;
     m->scaling = m->r ? cfg->lora_alpha / (float)m->r : 0.f;
-    const char* ng = getenv("VITLORA_NO_GRAPH");
-    m->use_graph = !(ng && ng[0] == '1');
+    m->use_graph = !env_flag("VITLORA_NO_GRAPH", false);
     // residual add of the 16-bit stream: 1 (default) = in the epilogue of the o / fc2 projection (EPI_RESID_H16: the stream row is
     // read two K steps ahead and x' = round16(x + acc + bias) stored -- the LayerNorm after it then moves 4 B per element instead
     // of 8); 0 (VITLORA_RESID=ln) = the projection stores a 16-bit delta and the LayerNorm adds it.  Same arithmetic, same rounding.
@@ -313,13 +321,13 @@ int vl_create(const vl_config* cfg, vl_model** out) {
     // Measured on one box: 502.5 / 505.5 / 506.8 img/s for ln / o / both -- the row read in the epilogue is nearly as exposed as
     // the LayerNorm bytes it saves; what it buys is ONE rounding per residual add instead of two (the delta, then the sum): the
     // reference-driven PGD-20 trajectory on ViT-B keeps 98.5 % of its pixels instead of 97.6 % (CPU storage simulation: 98.9 / 98.0).
-    { const char* re = getenv("VITLORA_RESID"); m->resid_epi = !re ? 2 : !strcmp(re, "ln") ? 0 : !strcmp(re, "o") ? 1 : 2; }
-    { const char* dr = getenv("VITLORA_DEAD_ROWS"); m->dead_rows = !(dr && dr[0] == '0'); }
-    { const char* fp = getenv("VITLORA_FUSE_PGD"); m->fuse_pgd = !(fp && fp[0] == '0'); }
-    if (const char* pc = getenv("VITLORA_PGD_CHAINS")) { const int v = atoi(pc); m->pgd_chains = v < 0 ? 0 : v > 2 ? 2 : v; }
-    { const char* fk = getenv("VITLORA_FUSE_DOWN_MIN_K"); if (fk) m->fuse_down_min_k = atoi(fk); }
-    { const char* sm = getenv("VITLORA_SMALL_M_ROWS"); if (sm) m->small_m_rows = atoi(sm); }
-    { const char* ai = getenv("VITLORA_ATTN_IMG"); m->attn_img_mode = ai ? (ai[0] == '1' ? 1 : 0) : -1; }
+    m->resid_epi = env_resid();
+    m->dead_rows = env_flag("VITLORA_DEAD_ROWS", true);
+    m->fuse_pgd = env_flag("VITLORA_FUSE_PGD", true);
+    m->pgd_chains = std::min(std::max(env_int("VITLORA_PGD_CHAINS", m->pgd_chains), 0), 2);
+    m->fuse_down_min_k = env_int("VITLORA_FUSE_DOWN_MIN_K", m->fuse_down_min_k);
+    m->small_m_rows = env_int("VITLORA_SMALL_M_ROWS", m->small_m_rows);
+    m->attn_img_mode = env_attn_img();
     { hipDeviceProp_t prop; m->num_cus = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256; }
     const int D = m->D, MLP = m->MLP, r = m->r;
     int rc;
@@ -1108,8 +1116,8 @@ int vl_pgd_init(float* adv, const float* x0, float eps, float lo, float hi, uint
 
 // VITLORA_GRAPH_DUMP=<file>: append the node list of a captured iteration (type, kernel name, grid, block, dynamic LDS)
 static void dump_graph(hipGraph_t graph) {
-    const char* path = getenv("VITLORA_GRAPH_DUMP");
-    if (!path || !path[0]) return;
+    const char* path = env_graph_dump();
+    if (!path) return;
     FILE* f = fopen(path, "a");
     if (!f) return;
     size_t n = 0;

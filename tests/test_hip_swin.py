@@ -211,38 +211,29 @@ def test_swin_two_chain_attack_equals_the_single_chain_attack(monkeypatch):
         assert torch.equal(outs["0"][2], outs[k][2]) and torch.equal(outs["0"][3], outs[k][3])
 
 
-def test_swin_fused_mlp_kernel_agrees_with_the_two_gemm_form(monkeypatch):
-    """csrc/mlp_fused.hip (round 5): stage 1's fc1 -> GELU -> fc2 (forward) and fc2 dgrad -> * gelu' -> fc1 dgrad (backward) in
-    one kernel each, the hidden activation kept in LDS (an experiment that is not the default: it removes the HBM traffic and is
-    slower, see csrc/swin.hip).  It runs for tall products only (batch >= 21 at 224 pixels), so this test
-    lowers the row threshold and compares logits, loss, input gradient and a PGD attack with the two-GEMM form on the same
-    handle weights -- same MFMA order per output element, so the results are expected to agree to fp16 rounding of identical
-    sums (printed: whether they are bit-equal) -- and with HF Swin through the oracle tolerance; odd batch 3 = ragged last tile."""
+def test_swin_narrow_stage_mlp_matches_hf_at_a_ragged_batch():
+    """Stage 1's MLP (C = 96: fc1 -> GELU -> fc2 forward, fc2 dgrad -> * gelu' -> fc1 dgrad backward, one GEMM launch per product)
+    at depths (2, 1, 1, 1) with LoRA r = 16 on fc2 and an odd batch 3 = ragged last tile, fp16:
+    logits and input gradient against HF Swin through the oracle tolerance, and a seeded PGD attack run twice on the same engine
+    must reproduce itself bit for bit.  (Until the fused stage-1 MLP kernel was removed this case compared that kernel with the
+    two-GEMM form; DESIGN.md section 6 keeps its measurements.)"""
     depths = (2, 1, 1, 1)
     m = hf_swin(12, seed=31, depths=depths)
     ab = add_lora(m, 16, 16.0, seed=32)
     g = torch.Generator().manual_seed(33)
     x = torch.rand(3, 3, 224, 224, generator=g)
     y = torch.randint(0, 12, (3,), generator=g)
-    outs = {}
-    for mode in ("0", "1"):
-        monkeypatch.setenv("VITLORA_SWIN_MLP_FUSED", mode)
-        monkeypatch.setenv("VITLORA_MLP_FUSED_MIN_ROWS", "128")
-        eng = make_engine(m, 12, 16, ab, depths=depths, precision="f16")
-        logits = eng.forward(x.cuda(), normalise=True).clone()
-        loss = eng.loss_ce(y.cuda()).clone()
-        gx = eng.backward_input(tuple(x.shape)).clone()
-        adv = eng.pgd_attack(x.cuda(), y.cuda(), 8 / 255, 2 / 255, 2, random_start=True, seed=2).clone()
-        eng.check()
-        torch.cuda.synchronize()
-        outs[mode] = (logits.cpu(), loss.cpu(), gx.cpu(), adv.cpu())
-        del eng
-    (l0, s0, g0, a0), (l1, s1, g1, a1) = outs["0"], outs["1"]
-    print("fused MLP vs two GEMMs: logits bit-equal", torch.equal(l0, l1), " grad rel", float((g1 - g0).norm() / g0.norm()),
-          " PGD pixels equal", float((a0 == a1).float().mean()))
+    eng = make_engine(m, 12, 16, ab, depths=depths, precision="f16")
+    l1 = eng.forward(x.cuda(), normalise=True).clone()
+    eng.loss_ce(y.cuda())
+    g1 = eng.backward_input(tuple(x.shape)).clone()
+    a0 = eng.pgd_attack(x.cuda(), y.cuda(), 8 / 255, 2 / 255, 2, random_start=True, seed=2).clone()
+    a1 = eng.pgd_attack(x.cuda(), y.cuda(), 8 / 255, 2 / 255, 2, random_start=True, seed=2).clone()
+    eng.check()
+    torch.cuda.synchronize()
+    l1, g1 = l1.cpu(), g1.cpu()
     assert torch.isfinite(l1).all() and torch.isfinite(g1).all()
-    assert float((l1 - l0).norm() / l0.norm()) < 1e-3 and float((g1 - g0).norm() / g0.norm()) < 2e-3
-    assert float((a0 == a1).float().mean()) > 0.99
+    assert torch.equal(a0, a1), float((a0 != a1).float().mean())
     xr = x.clone().requires_grad_(True)
     ref_logits = m((xr - MEAN) / STD).logits
     (ref_g,) = torch.autograd.grad(F.cross_entropy(ref_logits, y), xr)

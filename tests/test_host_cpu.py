@@ -309,6 +309,32 @@ def test_integration_md_indexes_every_abi_symbol():
     assert listed - syms == set(), sorted(listed - syms)
 
 
+def test_integration_md_lists_every_environment_switch_and_csrc_reads_them_one_way():
+    """INTEGRATION.md section 5 has one table row per VITLORA_* name that the library sources, the package's Python modules and the
+    command-line scripts mention, and no row for a name none of them mentions; in csrc/ a switch is read through env.h
+    (env_int / env_double / env_flag) -- the only other getenv calls are the three named helpers of vitlora.hip whose values
+    are neither a flag nor an integer (VITLORA_RESID, VITLORA_ATTN_IMG, VITLORA_GRAPH_DUMP)."""
+    import glob
+    csrc = os.path.join(ROOT, PKG, "csrc")
+    native = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    files = native + sorted(glob.glob(os.path.join(ROOT, PKG, "*.py")))
+    files += [os.path.join(ROOT, n) for n in ("train.py", "train_loras.py", "whitebox_attacks.py", "eval_compose.py", "patch_attack.py")]
+    used = set()
+    for f in files:
+        used |= set(re.findall(r"\bVITLORA_[A-Z0-9_]+", open(f).read()))
+    assert len(used) > 30          # the scan found the sources
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    sec = doc[doc.index("## 5. Environment switches"):]
+    rows = re.findall(r"^\| `(VITLORA_[A-Z0-9_]+)` \|", sec, re.M)
+    assert len(rows) == len(set(rows)), sorted(r for r in set(rows) if rows.count(r) > 1)
+    assert used - set(rows) == set(), sorted(used - set(rows))
+    assert set(rows) - used == set(), sorted(set(rows) - used)
+    helpers = ("int env_resid() {", "int env_attn_img() {", "const char* env_graph_dump() {")
+    stray = [(os.path.basename(f), line.strip()) for f in native if os.path.basename(f) != "env.h"
+             for line in open(f) if "getenv(" in line and not line.strip().startswith(helpers)]
+    assert stray == [], stray
+
+
 def test_bench_dump_outputs_is_float32_bounded_and_repeatable(tmp_path, monkeypatch):
     """bench.py --dump-outputs (host side, no GPU): a small output is written whole; one above the limit as whole images of a
     seeded, sorted choice of batch indices that is the same on every call; always float32 and never above 64 MB."""

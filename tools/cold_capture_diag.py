@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Cold-capture divergence (round-2 VERDICT item 6): in ONE fresh process, capture the PGD iteration WITHOUT the eager first
-iteration (VITLORA_COLD_CAPTURE=1), dump the captured graph's node list (VITLORA_GRAPH_DUMP), run the attack a few times
-and snapshot every saved activation after each run; then force a second (warm) capture and diff the two node lists.
+"""Cold-capture divergence (round-2 VERDICT item 6): in ONE fresh process, capture the PGD iteration cold -- no eager first
+iteration, which is what the library does since round 3 --, dump the captured graph's node list (VITLORA_GRAPH_DUMP), run the
+attack a few times and snapshot every saved activation after each run; then force a second (warm) capture and diff the two
+node lists.
 
     python tools/cold_capture_diag.py <steps> <out_prefix>
 """
@@ -11,7 +12,6 @@ import sys
 
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 prefix = sys.argv[2] if len(sys.argv) > 2 else "gpurun_out/cold"
-os.environ["VITLORA_COLD_CAPTURE"] = "1"
 os.environ["VITLORA_GRAPH_DUMP"] = prefix + "_nodes.txt"
 if os.path.exists(prefix + "_nodes.txt"):
     os.remove(prefix + "_nodes.txt")
