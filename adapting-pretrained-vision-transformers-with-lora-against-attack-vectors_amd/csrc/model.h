@@ -86,6 +86,14 @@ struct Workspace {
     float *f_dh, *f_dctx, *f_dqkv, *f_dz, *f_u, *f_xd, *f_tmp;
 };
 
+// One forward / backward chain: its activations and what its last forward left behind.  Every launch sequence takes the pass it
+// works on as an argument; nothing reads "the current pass" through the handle.
+struct Pass {
+    Workspace ws;
+    int B = 0, rows = 0;             // images and token rows (B * T) of the last forward; B = 0: the pass holds no forward
+    int norm = 0, train = 0, cls_only = 0, have_loss = 0;     // cls_only: that forward ran the last layer on the CLS rows only
+};
+
 struct GraphEntry {
     int B; float eps, alpha;
     hipGraphExec_t exec;
@@ -115,28 +123,25 @@ struct vl_model {
     float* flat = nullptr;
     int64_t flat_n = 0, cls_w_off = 0, cls_b_off = 0;
     int dirty = 1;                              // flat parameters changed since the last vl_lora_commit
-    VLNS::Workspace ws;
-    // state of the last forward
-    int cur_B = 0, cur_M = 0, cur_norm = 0, cur_train = 0, have_loss = 0;
+    VLNS::Pass main;                            // the whole-batch pass: every API call without chains, the gathered logits / loss with them
     uint64_t drop_seed = 0x5eed, drop_base = 0x5eed, drop_calls = 0;   // LoRA dropout: seed of the last train-mode forward
     // PGD graph cache (one executable graph per (batch, eps, alpha); staging buffers make it pointer-independent)
     std::vector<VLNS::GraphEntry> graphs;
     hipStream_t cap_stream = nullptr;
     // vl_pgd_attack at small batches (round 4): the batch runs as TWO independent half-batch chains, captured as parallel branches
     // of the one graph (fork / join by events on cap_stream / side_stream) -- a GEMM launch costs about one round more than its
-    // tiles (pipeline fill + exposed epilogue), and one chain's ends then meet the other's main loops.  Each chain has its own
-    // activation workspace (carved behind the main one for batches up to CHAIN_MAX_BATCH / 2).
+    // tiles (pipeline fill + exposed epilogue), and one chain's ends then meet the other's main loops.  Each chain is a pass of
+    // its own (half[c]: workspace carved behind the main one for batches up to CHAIN_MAX_BATCH / 2, and its own forward state).
     static constexpr int CHAIN_MAX_BATCH = 191;     // below the batch at which the per-image attention kernels take over (3/4 of 256 CUs): both forms of a batch then use the same kernels
-    VLNS::Workspace chain_ws[2];
-    int chain_batch = 0;          // images each chain workspace holds (0: none planned)
+    VLNS::Pass half[2];
+    int chain_batch = 0;          // images each half pass's workspace holds (0: none planned)
     int pgd_chains = 0;           // "pgd_chains" / VITLORA_PGD_CHAINS: 0 = by batch size (2 for 2 <= batch <= 191), 1 = never, 2 = whenever it fits
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // the same two chains behind vl_forward(train = 0) / vl_backward_input (opt-in, "api_chains": the adversarial-patch EoT step runs
-    // through these calls): logits are gathered into the main workspace, vl_loss_ce works on the whole batch, the backward splits again
+    // through these calls): logits are gathered into the main pass, vl_loss_ce works on the whole batch, the backward splits again
     int api_chains = 0;
-    int fwd_chains = 0;           // how the last vl_forward ran (0: one chain in the main workspace; 2: two chains)
-    int chain_B[2] = {0, 0}, chain_cls[2] = {0, 0};
+    int fwd_chains = 0;           // how the last vl_forward ran (0: one chain, the main pass; 2: the two half passes)
     int64_t n_captures = 0, n_commits = 0;
     int use_graph = 1;
     int resid_epi = 2;    // residual add of the 16-bit stream in the GEMM epilogue (EPI_RESID_H16): 1 = attention output projection, 2 = + fc2, 0 = LayerNorm-side
@@ -144,7 +149,6 @@ struct vl_model {
     int attn_img_mode = -1;   // VITLORA_ATTN_IMG: 1 / 0 force the per-image attention kernels on / off, -1 = by batch size
     int num_cus = 256;
     int dead_rows = 1;        // eval-mode forward / backward: last layer on CLS rows only (VITLORA_DEAD_ROWS=0 or vl_debug_set_dead_rows: off)
-    int cur_cls_only = 0;     // the last forward took that route
     int fuse_down_min_k = 2048;   // LoRA down projection inside the ping-pong GEMM for projections at least this deep (VITLORA_FUSE_DOWN_MIN_K)
     int small_m_rows = 16384;     // token rows up to which the "small batch" forms apply (VITLORA_SMALL_M_ROWS; batch <= 83 at T = 197)
     int fuse_pgd = 1;         // vl_pgd_attack: PGD step inside the patch-gradient epilogue (VITLORA_FUSE_PGD=0: separate K10 launch)
@@ -163,18 +167,18 @@ int vl_fail(int code, const char* fmt, ...);
         if (e_ != hipSuccess) return vl_fail(VL_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 namespace VLNS {
-bool vl_drop_on(const vl_model* m);
+bool vl_drop_on(const vl_model* m, const Pass& p);      // LoRA dropout applies to the forward that pass `p` holds
 
 // fp32 parity path (vitlora_f32.hip): reached through the fp16 build only (vl_create_bf16 refuses VL_PREC_F32)
 #ifdef VL_BF16
-static inline size_t f32_carve(vl_model*, int, int, char*, size_t off0) { return off0; }
-static inline int f32_forward(vl_model*, const float*, int, int, int, hipStream_t) { return VL_ERR_STATE; }
-static inline int f32_backward(vl_model*, float*, float*, hipStream_t) { return VL_ERR_STATE; }
+static inline size_t f32_carve(const vl_model*, Workspace&, int, char*, size_t off0) { return off0; }
+static inline int f32_forward(vl_model*, Pass&, const float*, int, int, hipStream_t) { return VL_ERR_STATE; }
+static inline int f32_backward(vl_model*, Pass&, float*, float*, hipStream_t) { return VL_ERR_STATE; }
 static inline int f32_init(int) { return 0; }
 #else
-size_t f32_carve(vl_model* m, int B, int train, char* base, size_t off0);
-int f32_forward(vl_model* m, const float* x, int B, int normalise, int train, hipStream_t s);
-int f32_backward(vl_model* m, float* grad_x, float* flat_grad, hipStream_t s);
+size_t f32_carve(const vl_model* m, Workspace& w, int train, char* base, size_t off0);      // w.Mpad / w.Mppad are set by the caller
+int f32_forward(vl_model* m, Pass& p, const float* x, int B, int normalise, hipStream_t s);  // p.train / p.rows are set by the caller
+int f32_backward(vl_model* m, Pass& p, float* grad_x, float* flat_grad, hipStream_t s);
 int f32_init(int device);     // kernel attributes; 0 = ok
 #endif
 }  // namespace VLNS

@@ -1058,30 +1058,50 @@ struct SLin {
     float* b16 = nullptr;                     // [outN] fp32, zero padded
     h16 *Ad = nullptr, *Bu = nullptr, *Bd = nullptr, *Au = nullptr;   // [64][inP], [outN][64] (scaled), [64][outP], [inN][64] (scaled)
 };
+// What is fixed at vl_swin_create / swin16_commit: weights, packed operands, LoRA slots and the 16-bit path's layout of a stage.
 struct SBlock {
     SLin qkv, o, fc1, fc2;
     float *ln1_g, *ln1_b, *ln2_g, *ln2_b, *table;
-    // saved by the forward
-    float *xa, *xb, *mean1, *rstd1, *mean2, *rstd2, *qkvbuf, *ctx, *lse, *z;
-    h16 *qkv16 = nullptr, *z16 = nullptr;     // 16-bit path: [Rp][P(3C)], gelu'(z) [Rp][P(4C)]
-    h16 *xa16 = nullptr, *xb16 = nullptr;     // 16-bit path (round 5): the residual stream entering LayerNorm 1 / LayerNorm 2, h16 [Rp][C]
 };
 struct SStage {
     int C, H, heads, depth;
     std::vector<SBlock> blocks;
     // downsample (absent after the last stage)
     float *mg_g = nullptr, *mg_b = nullptr, *Wred = nullptr;
-    float *mg = nullptr, *mmean = nullptr, *mrstd = nullptr;    // saved
-    // 16-bit path: per-stage scratch (strides are the stage's own padded widths: pad columns stay zero for ever)
+    h16 *Wred16 = nullptr, *WredT16 = nullptr;      // patch-merging reduction on h16 operands
+    // 16-bit path: layout of the stage's activations (strides are the stage's own padded widths: pad columns stay zero for ever)
     int CP = 0, C3P = 0, C4P = 0;             // GEMM dims: C, 3C, 4C rounded up to the 128-wide tiles (weights are zero padded)
     int LD = 0;                               // row stride of the GEMM RESULTS of width C (delta16, dh16, dctx16): LC, or the N-role width of C
     int LC = 0, L3 = 0, L4 = 0;               // row strides of the h16 activations: the padded dims, or C, 3C, 4C themselves
                                               // (stage 1: 96 / 288 / 384 -- a quarter fewer bytes on every tensor of the HBM-bound
                                               // stage; the GEMM then reads its last K columns from the NEXT row, times zero weights,
                                               // and skips the stores of the tile grid's extra columns: GemmArgs.n_store)
+};
+
+// What swin_carve lays out: the activations of ONE forward / backward chain and what its last forward left behind.  The handle owns
+// one for the whole batch and one per chain of vl_swin_pgd_attack; the launch sequences take the one they work on as an argument.
+struct SBlockWs {       // saved by the forward
+    float *xa, *xb, *mean1, *rstd1, *mean2, *rstd2, *qkvbuf, *ctx, *lse, *z;
+    h16 *qkv16 = nullptr, *z16 = nullptr;     // 16-bit path: [Rp][P(3C)], gelu'(z) [Rp][P(4C)]
+    h16 *xa16 = nullptr, *xb16 = nullptr;     // 16-bit path (round 5): the residual stream entering LayerNorm 1 / LayerNorm 2, h16 [Rp][C]
+};
+struct SStageWs {
+    std::vector<SBlockWs> blocks;
+    float *mg = nullptr, *mmean = nullptr, *mrstd = nullptr;    // patch merging, saved
+    // 16-bit path: per-stage scratch
     h16 *h16b = nullptr, *a16 = nullptr, *delta16 = nullptr, *ctx16 = nullptr, *t16 = nullptr, *u16 = nullptr;
     h16 *dz16 = nullptr, *dqkv16 = nullptr, *dh16 = nullptr, *dctx16 = nullptr, *gh16 = nullptr;
-    h16 *Wred16 = nullptr, *WredT16 = nullptr, *mg16 = nullptr, *g16 = nullptr;     // patch-merging reduction on h16 operands
+    h16 *mg16 = nullptr, *g16 = nullptr;
+};
+struct SwinWs {
+    int max_batch = 0, cur_B = 0, cur_norm = 0, have_loss = 0;     // (main workspace: max_batch < 0 = planned for -max_batch, not armed)
+    SStageWs st[4];
+    float *patches, *emb, *emean, *erstd, *xlast, *fmean, *frstd, *hfin, *pooled, *logits, *dlogits, *loss, *loss_img, *dpooled;
+    float *h, *a, *t, *u, *g0, *g1, *dbig, *dqkv, *grad_img, *stage_x0, *stage_adv;
+    int64_t* stage_labels;
+    float *gscale = nullptr, *inv_gscale = nullptr, *dlogits_s = nullptr;
+    h16 *patches16 = nullptr, *emb16 = nullptr;    // [R0][48], [R0][E]
+    h16 *xlast16 = nullptr, *hfin16 = nullptr, *dhfin16 = nullptr;      // 16-bit path: last stage's output stream, final LayerNorm output, its gradient
 };
 
 }  // namespace
@@ -1097,27 +1117,20 @@ struct vl_swin {
     float* flat = nullptr;
     int64_t flat_n = 0;
     std::vector<void*> allocs;
-    // workspace
-    int max_batch = 0, cur_B = 0, cur_norm = 0, have_loss = 0;
-    float *patches, *emb, *emean, *erstd, *xlast, *fmean, *frstd, *hfin, *pooled, *logits, *dlogits, *loss, *loss_img, *dpooled;
-    float *h, *a, *t, *u, *g0, *g1, *dbig, *dqkv, *grad_img, *stage_x0, *stage_adv;
-    int64_t* stage_labels;
+    SwinWs w;                // the whole-batch workspace
     int* err_flag = nullptr;
     float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-    float *gscale = nullptr, *inv_gscale = nullptr, *dlogits_s = nullptr;
     h16 *Wpe16 = nullptr, *WpeT16 = nullptr;      // 16-bit patch embedding (P = 4): [128][64] (rows >= E, columns >= 48 zero), [128][128] (rows >= 48 zero)
     float* bpe16 = nullptr;                        // [128] fp32, zero padded
-    h16 *patches16 = nullptr, *emb16 = nullptr;    // [R0][48], [R0][E]
     int pe16 = 0;                                  // the 16-bit patch embedding is in use (P == 4, E <= 128; VITLORA_SWIN_PE16=0: fp32 form of rounds 3-4)
-    h16 *xlast16 = nullptr, *hfin16 = nullptr, *dhfin16 = nullptr;      // 16-bit path: last stage's output stream, final LayerNorm output, its gradient
     int f16 = 0;             // cfg.reserved[0] == 1: 16-bit operand path for the blocks (embedding, merging and head stay fp32)
     int dirty = 1;           // packed h16 operands are stale (weights / adapters written since the last commit)
     // vl_swin_pgd_attack as TWO half-batch chains on two streams (round 5; the ViT path got them in round 4): stages 3-4 are
     // small-batch shaped at any batch (M = 50 176 / 12 544 rows: 392 / 147 tiles on 256 CUs) and the window kernels run one or two waves
-    // per SIMD, so the ends of one chain's kernels meet the main loops of the other's.  The chains are shallow copies of the handle
-    // (shared weights) whose workspace pointers are carved into the SAME planned bytes as the main workspace (never live together).
+    // per SIMD, so the ends of one chain's kernels meet the main loops of the other's.  Each chain is a workspace of its own, driven
+    // with this same handle; they are carved into the SAME planned bytes as the main workspace (never live together).
     static constexpr int MAXCH = 4;
-    vl_swin* chain[MAXCH] = {nullptr, nullptr, nullptr, nullptr};
+    SwinWs chain[MAXCH];
     int chain_batch = 0, chains_on = 2, chain_min = 32;      // VITLORA_SWIN_CHAINS = number of chains (0 / 1: off, default 2, at most 4); VITLORA_SWIN_CHAIN_MIN: smallest batch that is split
     hipStream_t side[MAXCH - 1] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -1147,23 +1160,23 @@ GemmF32 gm(const float* A, int lda, const float* W, int ldw, int transW, int M, 
 }
 
 // y = x W^T + b (+ R) + sum over adapted modules of s * (x A^T) B^T        (peft lora.Linear, eval mode)
-void lin_fwd(vl_swin* m, const SLin& ln, const float* x, int M, float* y, const float* R, hipStream_t s) {
+void lin_fwd(const vl_swin* m, SwinWs& w, const SLin& ln, const float* x, int M, float* y, const float* R, hipStream_t s) {
     GemmF32 g = gm(x, ln.in, ln.W, ln.in, 0, M, ln.out, ln.in, y, ln.out);
     g.bias = ln.b; g.R = R; g.ldr = ln.out;
     k_gemm_f32(g, s);
     for (const SLora& sl : ln.slots) {
-        k_gemm_f32(gm(x, ln.in, sl.A, ln.in, 0, M, m->r, ln.in, m->t, 64), s);
-        GemmF32 u = gm(m->t, 64, sl.B, m->r, 0, M, sl.out, m->r, y + sl.row_off, ln.out);
+        k_gemm_f32(gm(x, ln.in, sl.A, ln.in, 0, M, m->r, ln.in, w.t, 64), s);
+        GemmF32 u = gm(w.t, 64, sl.B, m->r, 0, M, sl.out, m->r, y + sl.row_off, ln.out);
         u.alpha = m->scaling; u.R = y + sl.row_off; u.ldr = ln.out;
         k_gemm_f32(u, s);
     }
 }
 // dx = dy W + sum of s * (dy B) A
-void lin_dgrad(vl_swin* m, const SLin& ln, const float* dy, int M, float* dx, hipStream_t s) {
+void lin_dgrad(const vl_swin* m, SwinWs& w, const SLin& ln, const float* dy, int M, float* dx, hipStream_t s) {
     k_gemm_f32(gm(dy, ln.out, ln.W, ln.in, 1, M, ln.in, ln.out, dx, ln.in), s);
     for (const SLora& sl : ln.slots) {
-        k_gemm_f32(gm(dy + sl.row_off, ln.out, sl.B, m->r, 1, M, m->r, sl.out, m->u, 64), s);
-        GemmF32 a = gm(m->u, 64, sl.A, ln.in, 1, M, ln.in, m->r, dx, ln.in);
+        k_gemm_f32(gm(dy + sl.row_off, ln.out, sl.B, m->r, 1, M, m->r, sl.out, w.u, 64), s);
+        GemmF32 a = gm(w.u, 64, sl.A, ln.in, 1, M, ln.in, m->r, dx, ln.in);
         a.alpha = m->scaling; a.R = dx; a.ldr = ln.in;
         k_gemm_f32(a, s);
     }
@@ -1217,7 +1230,7 @@ void swin16_commit(vl_swin* m, hipStream_t s) {
 }
 
 // y = x W^T + b (+ LoRA as one extra K tile), epilogue `epi`; x [Mp][inP] h16
-void lin16_fwd(vl_swin* m, SStage& st, const SLin& ln, const h16* x, int ldx, int Mp, int M, GemmArgs g, int epi, hipStream_t s) {
+void lin16_fwd(const vl_swin* m, SStageWs& sw, const SLin& ln, const h16* x, int ldx, int Mp, int M, GemmArgs g, int epi, hipStream_t s) {
     g.A1 = x; g.lda1 = ldx; g.W1 = ln.W16; g.ldw1 = ln.inP; g.K1 = ln.inP;
     g.M = Mp; g.Mvalid = M; g.N = ln.outN; g.bias = ln.b16; g.no_pp = 1;
     g.n_store = g.ldc < ln.outN ? ln.out : 0;                      // unpadded result rows (ldc = out)
@@ -1229,15 +1242,15 @@ void lin16_fwd(vl_swin* m, SStage& st, const SLin& ln, const h16* x, int ldx, in
         if (!gemm_stream_fuses_down(g, epi)) {          // t = x Ad^T as its own skinny GEMM, read back as the LoRA K tile's A operand
             g.down_W = nullptr; g.down_ldw = 0; g.down_groups = 0;
             GemmArgs d = ga(x, ldx, ln.Ad, ln.inP, ln.inP, Mp, 64);
-            d.Mvalid = M; d.C = st.t16; d.ldc = 64; d.n_algo = m->r * (int)ln.slots.size();
+            d.Mvalid = M; d.C = sw.t16; d.ldc = 64; d.n_algo = m->r * (int)ln.slots.size();
             launch_gemm(d, EPI_STORE_H16, 64, s);
-            g.A2 = st.t16; g.lda2 = 64;
+            g.A2 = sw.t16; g.lda2 = 64;
         }
     }
     launch_gemm(g, epi, 128, s);
 }
 // dx = dy W (+ LoRA), dy [Mp][outP] h16
-void lin16_dgrad(vl_swin* m, SStage& st, const SLin& ln, const h16* dy, int ldy, int Mp, int M, GemmArgs g, int epi, hipStream_t s) {
+void lin16_dgrad(const vl_swin* m, SStageWs& sw, const SLin& ln, const h16* dy, int ldy, int Mp, int M, GemmArgs g, int epi, hipStream_t s) {
     g.A1 = dy; g.lda1 = ldy; g.W1 = ln.WT16; g.ldw1 = ln.outP; g.K1 = ln.outP;
     g.M = Mp; g.Mvalid = M; g.N = ln.inN; g.bias = nullptr; g.no_pp = 1;
     g.n_store = g.ldc < ln.inN ? ln.in : 0;
@@ -1248,60 +1261,60 @@ void lin16_dgrad(vl_swin* m, SStage& st, const SLin& ln, const h16* dy, int ldy,
         if (!gemm_stream_fuses_down(g, epi)) {
             g.down_W = nullptr; g.down_ldw = 0; g.down_groups = 0;
             GemmArgs d = ga(dy, ldy, ln.Bd, ln.outP, ln.outP, Mp, 64);
-            d.Mvalid = M; d.C = st.u16; d.ldc = 64; d.n_algo = m->r;
+            d.Mvalid = M; d.C = sw.u16; d.ldc = 64; d.n_algo = m->r;
             launch_gemm(d, EPI_STORE_H16, 64, s);
-            g.A2 = st.u16; g.lda2 = 64;
+            g.A2 = sw.u16; g.lda2 = 64;
         }
     }
     launch_gemm(g, epi, 128, s);
 }
 
 // One Swin block, forward, on the 16-bit residual stream (round 5).  x_prev16: the stream entering the PREVIOUS block's MLP
-// (its xb16) when `add_delta` -- st.delta16 then still holds that block's fc2 output and LayerNorm 1 adds the two on its way
-// (x' = round16(x + delta) -> bk.xa16); otherwise bk.xa16 already is this block's input (first block of a stage).  Leaves the
-// block's own fc2 output in st.delta16 (to be added by whoever consumes the stream next) and the stream before it in bk.xb16.
-void swin16_block_fwd(vl_swin* m, SStage& st, SBlock& bk, const h16* x_prev16, bool add_delta, int B, int shift, hipStream_t s) {
+// (its xb16) when `add_delta` -- sw.delta16 then still holds that block's fc2 output and LayerNorm 1 adds the two on its way
+// (x' = round16(x + delta) -> bw.xa16); otherwise bw.xa16 already is this block's input (first block of a stage).  Leaves the
+// block's own fc2 output in sw.delta16 (to be added by whoever consumes the stream next) and the stream before it in bw.xb16.
+void swin16_block_fwd(const vl_swin* m, const SStage& st, SStageWs& sw, const SBlock& bk, SBlockWs& bw, const h16* x_prev16, bool add_delta, int B, int shift, hipStream_t s) {
     const int Cs = st.C, Hs = st.H, M = B * Hs * Hs, Mp = (int)round_up(M, 128);
     const int nW = (Hs / WS) * (Hs / WS);
     GemmArgs g;
-    if (add_delta) sw_ln_fwd16<false>(x_prev16, Cs, st.delta16, st.LD, bk.xa16, Cs, st.h16b, st.LC, bk.mean1, bk.rstd1, bk.ln1_g, bk.ln1_b, M, Cs, m->cfg.ln_eps, m->err_flag, s);
-    else sw_ln_fwd16<false>(bk.xa16, Cs, nullptr, 0, nullptr, 0, st.h16b, st.LC, bk.mean1, bk.rstd1, bk.ln1_g, bk.ln1_b, M, Cs, m->cfg.ln_eps, m->err_flag, s);
-    memset(&g, 0, sizeof g); g.C = bk.qkv16; g.ldc = st.L3;
-    lin16_fwd(m, st, bk.qkv, st.h16b, st.LC, Mp, M, g, EPI_STORE_H16, s);
+    if (add_delta) sw_ln_fwd16<false>(x_prev16, Cs, sw.delta16, st.LD, bw.xa16, Cs, sw.h16b, st.LC, bw.mean1, bw.rstd1, bk.ln1_g, bk.ln1_b, M, Cs, m->cfg.ln_eps, m->err_flag, s);
+    else sw_ln_fwd16<false>(bw.xa16, Cs, nullptr, 0, nullptr, 0, sw.h16b, st.LC, bw.mean1, bw.rstd1, bk.ln1_g, bk.ln1_b, M, Cs, m->cfg.ln_eps, m->err_flag, s);
+    memset(&g, 0, sizeof g); g.C = bw.qkv16; g.ldc = st.L3;
+    lin16_fwd(m, sw, bk.qkv, sw.h16b, st.LC, Mp, M, g, EPI_STORE_H16, s);
     const int64_t witems = (int64_t)B * nW * st.heads;
     if (g_poison_lds) vl_poison_lds(s);      // test hook (prof.h): the window kernels keep K / V / Q / dO of a window in LDS
     hipLaunchKernelGGL(win16_fwd_kernel, dim3(win16_grid(witems, st.heads, 8)), dim3(64), 0, s,
-                       bk.qkv16, st.L3, bk.table, st.ctx16, st.LC, bk.lse, B, Hs, Hs, Cs, st.heads, shift, witems);
-    memset(&g, 0, sizeof g); g.C = st.delta16; g.ldc = st.LD;
-    lin16_fwd(m, st, bk.o, st.ctx16, st.LC, Mp, M, g, EPI_STORE_H16, s);
+                       bw.qkv16, st.L3, bk.table, sw.ctx16, st.LC, bw.lse, B, Hs, Hs, Cs, st.heads, shift, witems);
+    memset(&g, 0, sizeof g); g.C = sw.delta16; g.ldc = st.LD;
+    lin16_fwd(m, sw, bk.o, sw.ctx16, st.LC, Mp, M, g, EPI_STORE_H16, s);
     // LayerNorm 2 (+ residual add of the attention output: xa16 + delta -> xb16)
-    sw_ln_fwd16<false>(bk.xa16, Cs, st.delta16, st.LD, bk.xb16, Cs, st.h16b, st.LC, bk.mean2, bk.rstd2, bk.ln2_g, bk.ln2_b, M, Cs, m->cfg.ln_eps, m->err_flag, s);
-    memset(&g, 0, sizeof g); g.C = st.a16; g.ldc = st.L4; g.C2 = bk.z16; g.ldc2 = st.L4;
-    lin16_fwd(m, st, bk.fc1, st.h16b, st.LC, Mp, M, g, EPI_GELU, s);
-    memset(&g, 0, sizeof g); g.C = st.delta16; g.ldc = st.LD;
-    lin16_fwd(m, st, bk.fc2, st.a16, st.L4, Mp, M, g, EPI_STORE_H16, s);
+    sw_ln_fwd16<false>(bw.xa16, Cs, sw.delta16, st.LD, bw.xb16, Cs, sw.h16b, st.LC, bw.mean2, bw.rstd2, bk.ln2_g, bk.ln2_b, M, Cs, m->cfg.ln_eps, m->err_flag, s);
+    memset(&g, 0, sizeof g); g.C = sw.a16; g.ldc = st.L4; g.C2 = bw.z16; g.ldc2 = st.L4;
+    lin16_fwd(m, sw, bk.fc1, sw.h16b, st.LC, Mp, M, g, EPI_GELU, s);
+    memset(&g, 0, sizeof g); g.C = sw.delta16; g.ldc = st.LD;
+    lin16_fwd(m, sw, bk.fc2, sw.a16, st.L4, Mp, M, g, EPI_STORE_H16, s);
 }
 
-// One Swin block, backward.  st.gh16 (h16, row stride st.LC) holds the gradient w.r.t. the block's output stream and is updated
+// One Swin block, backward.  sw.gh16 (h16, row stride st.LC) holds the gradient w.r.t. the block's output stream and is updated
 // IN PLACE to the gradient w.r.t. its input stream: it is the residual-gradient stream and the A operand of the dgrad GEMMs.
-void swin16_block_bwd(vl_swin* m, SStage& st, SBlock& bk, int B, int shift, hipStream_t s) {
+void swin16_block_bwd(const vl_swin* m, const SStage& st, SStageWs& sw, const SBlock& bk, SBlockWs& bw, int B, int shift, hipStream_t s) {
     const int Cs = st.C, Hs = st.H, M = B * Hs * Hs, Mp = (int)round_up(M, 128);
     const int nW = (Hs / WS) * (Hs / WS);
     GemmArgs g;
-    memset(&g, 0, sizeof g); g.C = st.dz16; g.ldc = st.L4; g.R = bk.z16; g.ldr = st.L4;
-    lin16_dgrad(m, st, bk.fc2, st.gh16, st.LC, Mp, M, g, EPI_GELU_BWD, s);                         // d(z) = (d(out) Wfc2) * gelu'(z)
-    memset(&g, 0, sizeof g); g.C = st.dh16; g.ldc = st.LD;
-    lin16_dgrad(m, st, bk.fc1, st.dz16, st.L4, Mp, M, g, EPI_STORE_H16, s);
-    sw_ln_bwd16<false, false>(st.dh16, st.LD, bk.xb16, Cs, bk.mean2, bk.rstd2, bk.ln2_g, st.gh16, st.gh16, st.LC, M, Cs, m->err_flag, s);
-    memset(&g, 0, sizeof g); g.C = st.dctx16; g.ldc = st.LD;
-    lin16_dgrad(m, st, bk.o, st.gh16, st.LC, Mp, M, g, EPI_STORE_H16, s);
+    memset(&g, 0, sizeof g); g.C = sw.dz16; g.ldc = st.L4; g.R = bw.z16; g.ldr = st.L4;
+    lin16_dgrad(m, sw, bk.fc2, sw.gh16, st.LC, Mp, M, g, EPI_GELU_BWD, s);                         // d(z) = (d(out) Wfc2) * gelu'(z)
+    memset(&g, 0, sizeof g); g.C = sw.dh16; g.ldc = st.LD;
+    lin16_dgrad(m, sw, bk.fc1, sw.dz16, st.L4, Mp, M, g, EPI_STORE_H16, s);
+    sw_ln_bwd16<false, false>(sw.dh16, st.LD, bw.xb16, Cs, bw.mean2, bw.rstd2, bk.ln2_g, sw.gh16, sw.gh16, st.LC, M, Cs, m->err_flag, s);
+    memset(&g, 0, sizeof g); g.C = sw.dctx16; g.ldc = st.LD;
+    lin16_dgrad(m, sw, bk.o, sw.gh16, st.LC, Mp, M, g, EPI_STORE_H16, s);
     const int64_t witems = (int64_t)B * nW * st.heads;
     if (g_poison_lds) vl_poison_lds(s);      // test hook (prof.h): the window kernels keep K / V / Q / dO of a window in LDS
     hipLaunchKernelGGL(win16_bwd_kernel, dim3(win16_grid(witems, st.heads, g_win_bwd_per_cu)), dim3(64), 0, s,
-                       bk.qkv16, st.L3, bk.table, st.dctx16, st.LD, bk.lse, st.dqkv16, B, Hs, Hs, Cs, st.heads, shift, witems);
-    memset(&g, 0, sizeof g); g.C = st.dh16; g.ldc = st.LD;
-    lin16_dgrad(m, st, bk.qkv, st.dqkv16, st.L3, Mp, M, g, EPI_STORE_H16, s);
-    sw_ln_bwd16<false, false>(st.dh16, st.LD, bk.xa16, Cs, bk.mean1, bk.rstd1, bk.ln1_g, st.gh16, st.gh16, st.LC, M, Cs, m->err_flag, s);
+                       bw.qkv16, st.L3, bk.table, sw.dctx16, st.LD, bw.lse, sw.dqkv16, B, Hs, Hs, Cs, st.heads, shift, witems);
+    memset(&g, 0, sizeof g); g.C = sw.dh16; g.ldc = st.LD;
+    lin16_dgrad(m, sw, bk.qkv, sw.dqkv16, st.L3, Mp, M, g, EPI_STORE_H16, s);
+    sw_ln_bwd16<false, false>(sw.dh16, st.LD, bw.xa16, Cs, bw.mean1, bw.rstd1, bk.ln1_g, sw.gh16, sw.gh16, st.LC, M, Cs, m->err_flag, s);
 }
 
 int parse2(const char* name, const char* pfx, int* a, const char** rest) {
@@ -1366,6 +1379,12 @@ int vl_swin_create(const vl_swin_config* cfg, vl_swin** out) {
         st.C = m->E << i; st.H = res; st.heads = cfg->heads[i]; st.depth = cfg->depths[i];
         st.blocks.resize(st.depth);
         const int Cs = st.C;
+        if (m->f16) {
+            st.CP = padc(Cs); st.C3P = padc(3 * Cs); st.C4P = padc(4 * Cs);
+            const bool unpad = ((m->unpad_stages >> i) & 1) && Cs % 32 == 0;
+            st.LC = unpad ? Cs : st.CP; st.L3 = unpad ? 3 * Cs : npad(Cs, st.C3P); st.L4 = unpad ? 4 * Cs : st.C4P;
+            st.LD = unpad ? Cs : npad(Cs, st.CP);
+        }
         for (SBlock& bk : st.blocks) {
             bk.qkv.out = 3 * Cs; bk.qkv.in = Cs; bk.o.out = Cs; bk.o.in = Cs;
             bk.fc1.out = 4 * Cs; bk.fc1.in = Cs; bk.fc2.out = Cs; bk.fc2.in = 4 * Cs;
@@ -1426,13 +1445,8 @@ int vl_swin_create(const vl_swin_config* cfg, vl_swin** out) {
     return VL_OK;
 }
 
-static void swin_drop_chains(vl_swin* m) {
-    for (int c = 0; c < vl_swin::MAXCH; ++c) { delete m->chain[c]; m->chain[c] = nullptr; }      // (non-owning copies: no device memory of their own)
-    m->chain_batch = 0;
-}
 int vl_swin_destroy(vl_swin* m) {
     if (!m) return VL_OK;
-    swin_drop_chains(m);
     for (hipStream_t sd : m->side) if (sd) (void)hipStreamDestroy(sd);
     if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
     if (m->ev_join) (void)hipEventDestroy(m->ev_join);
@@ -1521,7 +1535,10 @@ int vl_swin_set_normalization(vl_swin* m, const float mean[3], const float stdv[
     return VL_OK;
 }
 
-static size_t swin_carve(vl_swin* m, int B, char* base) {
+// Lays the activations of up to B images out from `base` into `w` (which then holds no forward) and returns the bytes they take;
+// base == nullptr: a size query, `w` is a throw-away.
+static size_t swin_carve(const vl_swin* m, SwinWs& w, int B, char* base) {
+    w.max_batch = base ? B : 0; w.cur_B = 0; w.have_loss = 0;
     size_t off = 0;
     auto take = [&](size_t bytes) -> float* {
         char* p = base ? base + off : nullptr;
@@ -1530,66 +1547,64 @@ static size_t swin_carve(vl_swin* m, int B, char* base) {
     };
     const int L0 = m->G0 * m->G0, PK = 3 * m->P * m->P;
     const int64_t R0 = round_up((int64_t)B * L0, 64);
-    m->patches = take((size_t)R0 * PK * 4);
+    w.patches = take((size_t)R0 * PK * 4);
     if (m->pe16) {       // (rows rounded up to the GEMM's 128-row tiles: the projection reads and stores whole tiles)
         const int64_t R128 = round_up((int64_t)B * L0, 128);
-        m->patches16 = (h16*)take((size_t)R128 * PK * 2 + 512); m->emb16 = (h16*)take((size_t)R128 * m->E * 2 + 512);
+        w.patches16 = (h16*)take((size_t)R128 * PK * 2 + 512); w.emb16 = (h16*)take((size_t)R128 * m->E * 2 + 512);
     }
-    m->emb = take((size_t)R0 * m->E * 4); m->emean = take((size_t)R0 * 4); m->erstd = take((size_t)R0 * 4);
+    w.emb = take((size_t)R0 * m->E * 4); w.emean = take((size_t)R0 * 4); w.erstd = take((size_t)R0 * 4);
     size_t big = 0;
     for (int i = 0; i < 4; ++i) {
-        SStage& st = m->stages[i];
+        const SStage& st = m->stages[i];
+        SStageWs& sw = w.st[i];
+        sw.blocks.resize(st.depth);
         const int64_t R = round_up((int64_t)B * st.H * st.H, 512);     // (a quarter of it is still a multiple of the GEMM row tile)
-        for (SBlock& bk : st.blocks) {
-            bk.mean1 = take((size_t)R * 4); bk.rstd1 = take((size_t)R * 4); bk.mean2 = take((size_t)R * 4); bk.rstd2 = take((size_t)R * 4);
-            bk.lse = take((size_t)R * st.heads * 4);
+        for (SBlockWs& bw : sw.blocks) {
+            bw.mean1 = take((size_t)R * 4); bw.rstd1 = take((size_t)R * 4); bw.mean2 = take((size_t)R * 4); bw.rstd2 = take((size_t)R * 4);
+            bw.lse = take((size_t)R * st.heads * 4);
             if (m->f16) continue;              // the 16-bit path keeps its streams and activations as h16 tensors (below)
-            bk.xa = take((size_t)R * st.C * 4); bk.xb = take((size_t)R * st.C * 4);
-            bk.qkvbuf = take((size_t)R * 3 * st.C * 4); bk.ctx = take((size_t)R * st.C * 4);
-            bk.z = take((size_t)R * 4 * st.C * 4);
+            bw.xa = take((size_t)R * st.C * 4); bw.xb = take((size_t)R * st.C * 4);
+            bw.qkvbuf = take((size_t)R * 3 * st.C * 4); bw.ctx = take((size_t)R * st.C * 4);
+            bw.z = take((size_t)R * 4 * st.C * 4);
         }
         if (m->f16) {
             const int64_t Rp = round_up((int64_t)B * st.H * st.H, 128);
-            st.CP = padc(st.C); st.C3P = padc(3 * st.C); st.C4P = padc(4 * st.C);
-            const bool unpad = ((m->unpad_stages >> i) & 1) && st.C % 32 == 0;
-            st.LC = unpad ? st.C : st.CP; st.L3 = unpad ? 3 * st.C : npad(st.C, st.C3P); st.L4 = unpad ? 4 * st.C : st.C4P;
-            st.LD = unpad ? st.C : npad(st.C, st.CP);
             // (+ 512 B: a GEMM whose A rows are narrower than its K reads that far past the last row)
             auto th = [&](size_t n) { return (h16*)take(n * 2 + 512); };
-            for (SBlock& bk : st.blocks) {
-                bk.qkv16 = th((size_t)Rp * npad(st.C, st.C3P)); bk.z16 = th((size_t)Rp * st.C4P);
-                bk.xa16 = th((size_t)Rp * st.C); bk.xb16 = th((size_t)Rp * st.C);
+            for (SBlockWs& bw : sw.blocks) {
+                bw.qkv16 = th((size_t)Rp * npad(st.C, st.C3P)); bw.z16 = th((size_t)Rp * st.C4P);
+                bw.xa16 = th((size_t)Rp * st.C); bw.xb16 = th((size_t)Rp * st.C);
             }
             const size_t CD = (size_t)npad(st.C, st.CP);
-            st.h16b = th((size_t)Rp * st.CP); st.a16 = th((size_t)Rp * st.C4P); st.delta16 = th((size_t)Rp * CD);
-            st.ctx16 = th((size_t)Rp * st.CP); st.t16 = th((size_t)Rp * 64); st.u16 = th((size_t)Rp * 64);
-            st.dz16 = th((size_t)Rp * st.C4P); st.dqkv16 = th((size_t)Rp * npad(st.C, st.C3P)); st.dh16 = th((size_t)Rp * CD);
-            st.dctx16 = th((size_t)Rp * CD); st.gh16 = th((size_t)Rp * st.CP);
-            if (i < 3) { const int64_t Rq = round_up(Rp / 4, 128); st.mg16 = th((size_t)Rq * 4 * st.C); st.g16 = th((size_t)Rq * 2 * st.C); }
+            sw.h16b = th((size_t)Rp * st.CP); sw.a16 = th((size_t)Rp * st.C4P); sw.delta16 = th((size_t)Rp * CD);
+            sw.ctx16 = th((size_t)Rp * st.CP); sw.t16 = th((size_t)Rp * 64); sw.u16 = th((size_t)Rp * 64);
+            sw.dz16 = th((size_t)Rp * st.C4P); sw.dqkv16 = th((size_t)Rp * npad(st.C, st.C3P)); sw.dh16 = th((size_t)Rp * CD);
+            sw.dctx16 = th((size_t)Rp * CD); sw.gh16 = th((size_t)Rp * st.CP);
+            if (i < 3) { const int64_t Rq = round_up(Rp / 4, 128); sw.mg16 = th((size_t)Rq * 4 * st.C); sw.g16 = th((size_t)Rq * 2 * st.C); }
         }
-        if (i < 3) { if (!m->f16) st.mg = take((size_t)R / 4 * 4 * st.C * 4 + 1024); st.mmean = take((size_t)R); st.mrstd = take((size_t)R); }
+        if (i < 3) { if (!m->f16) sw.mg = take((size_t)R / 4 * 4 * st.C * 4 + 1024); sw.mmean = take((size_t)R); sw.mrstd = take((size_t)R); }
         if ((size_t)R * 4 * st.C > big) big = (size_t)R * 4 * st.C;
     }
     const int Cl = m->E << 3, Ll = m->stages[3].H * m->stages[3].H;
-    m->xlast = take((size_t)round_up((int64_t)B * Ll, 64) * Cl * 4);
+    w.xlast = take((size_t)round_up((int64_t)B * Ll, 64) * Cl * 4);
     if (m->f16) {
         const size_t nl = (size_t)round_up((int64_t)B * Ll, 64) * Cl * 2;
-        m->xlast16 = (h16*)take(nl); m->hfin16 = (h16*)take(nl); m->dhfin16 = (h16*)take(nl);
+        w.xlast16 = (h16*)take(nl); w.hfin16 = (h16*)take(nl); w.dhfin16 = (h16*)take(nl);
     }
-    m->fmean = take((size_t)B * Ll * 4 + 256); m->frstd = take((size_t)B * Ll * 4 + 256);
-    m->hfin = take((size_t)round_up((int64_t)B * Ll, 64) * Cl * 4);
-    m->pooled = take((size_t)B * Cl * 4); m->dpooled = take((size_t)B * Cl * 4);
-    m->logits = take((size_t)B * m->C * 4); m->dlogits = take((size_t)B * m->C * 4);
-    m->loss = take(256); m->loss_img = take((size_t)B * 4);
-    m->gscale = take((size_t)B * 4); m->inv_gscale = take((size_t)B * 4); m->dlogits_s = take((size_t)B * m->C * 4);
+    w.fmean = take((size_t)B * Ll * 4 + 256); w.frstd = take((size_t)B * Ll * 4 + 256);
+    w.hfin = take((size_t)round_up((int64_t)B * Ll, 64) * Cl * 4);
+    w.pooled = take((size_t)B * Cl * 4); w.dpooled = take((size_t)B * Cl * 4);
+    w.logits = take((size_t)B * m->C * 4); w.dlogits = take((size_t)B * m->C * 4);
+    w.loss = take(256); w.loss_img = take((size_t)B * 4);
+    w.gscale = take((size_t)B * 4); w.inv_gscale = take((size_t)B * 4); w.dlogits_s = take((size_t)B * m->C * 4);
     if (m->f16) big = 64;       // the 16-bit path has no fp32 activation scratch (round 5: h16 streams); g1 serves the embedding backward
-    m->h = take(big * 4); m->a = take(big * 4); m->dbig = take(big * 4);
-    m->dqkv = take(big * 4);
-    m->t = take((size_t)R0 * 64 * 4); m->u = take((size_t)R0 * 64 * 4);
-    m->g0 = take((size_t)R0 * m->E * 4 + big); m->g1 = take((size_t)R0 * m->E * 4 + big);
+    w.h = take(big * 4); w.a = take(big * 4); w.dbig = take(big * 4);
+    w.dqkv = take(big * 4);
+    w.t = take((size_t)R0 * 64 * 4); w.u = take((size_t)R0 * 64 * 4);
+    w.g0 = take((size_t)R0 * m->E * 4 + big); w.g1 = take((size_t)R0 * m->E * 4 + big);
     const size_t img = (size_t)B * 3 * m->S * m->S * 4;
-    m->grad_img = take(img); m->stage_x0 = take(img); m->stage_adv = take(img);
-    m->stage_labels = (int64_t*)take((size_t)B * 8);
+    w.grad_img = take(img); w.stage_x0 = take(img); w.stage_adv = take(img);
+    w.stage_labels = (int64_t*)take((size_t)B * 8);
     return off;
 }
 
@@ -1598,14 +1613,11 @@ static int swin_chain_images(const vl_swin* m, int max_batch) {
     const int nc = m->chains_on;
     return (m->f16 && nc >= 2 && max_batch >= m->chain_min && max_batch >= nc) ? (max_batch + nc - 1) / nc : 0;
 }
-static size_t swin_plan_bytes(vl_swin* m, int max_batch) {
-    const size_t main_need = swin_carve(m, max_batch, nullptr);
+static size_t swin_plan_bytes(const vl_swin* m, int max_batch) {
+    SwinWs scratch;
+    const size_t main_need = swin_carve(m, scratch, max_batch, nullptr);
     const int cb = swin_chain_images(m, max_batch);
-    if (!cb) return main_need;
-    vl_swin tmp(*m);
-    tmp.allocs.clear();
-    const size_t one = swin_carve(&tmp, cb, nullptr);
-    return std::max(main_need, (size_t)m->chains_on * one);
+    return cb ? std::max(main_need, (size_t)m->chains_on * swin_carve(m, scratch, cb, nullptr)) : main_need;
 }
 
 int vl_swin_plan(vl_swin* m, int max_batch, size_t* bytes) {
@@ -1619,35 +1631,23 @@ int vl_swin_plan(vl_swin* m, int max_batch, size_t* bytes) {
                            "32-bit operand offsets reach; split the batch", max_batch, (long long)rows, (long long)wide);
     }
     *bytes = swin_plan_bytes(m, max_batch);
-    m->max_batch = -max_batch;          // planned, not armed
+    m->w.max_batch = -max_batch;       // planned, not armed
     return VL_OK;
 }
 
 int vl_swin_set_workspace(vl_swin* m, void* ws, size_t bytes) {
     if (!m || !ws) return vl_fail(VL_ERR_ARG, "null argument");
-    if (m->max_batch >= 0) return vl_fail(VL_ERR_STATE, "vl_swin_set_workspace before vl_swin_plan");
-    const int B = -m->max_batch;
+    if (m->w.max_batch >= 0) return vl_fail(VL_ERR_STATE, "vl_swin_set_workspace before vl_swin_plan");
+    const int B = -m->w.max_batch;
     if (((uintptr_t)ws) & 255) return vl_fail(VL_ERR_ARG, "workspace must be 256-byte aligned");
     const size_t need = swin_plan_bytes(m, B);
     if (bytes < need) return vl_fail(VL_ERR_ARG, "workspace too small: %zu < %zu", bytes, need);
-    swin_carve(m, B, (char*)ws);
     if (hipMemset(ws, 0, need) != hipSuccess) return vl_fail(VL_ERR_HIP, "hipMemset(workspace) failed");
-    m->max_batch = B;
-    m->cur_B = 0;
-    swin_drop_chains(m);
-    if (const int cb = swin_chain_images(m, B)) {
-        size_t one = 0;
-        for (int c = 0; c < m->chains_on; ++c) {
-            vl_swin* ch = new vl_swin(*m);          // weights shared (pointers), workspace pointers re-carved below
-            ch->allocs.clear(); ch->ev_fork = ch->ev_join = nullptr;
-            for (int k = 0; k < vl_swin::MAXCH; ++k) ch->chain[k] = nullptr;
-            for (int k = 0; k < vl_swin::MAXCH - 1; ++k) ch->side[k] = nullptr;
-            one = swin_carve(ch, cb, nullptr);
-            swin_carve(ch, cb, (char*)ws + (size_t)c * one);
-            ch->max_batch = cb; ch->cur_B = 0; ch->have_loss = 0;
-            m->chain[c] = ch;
-        }
-        m->chain_batch = cb;
+    swin_carve(m, m->w, B, (char*)ws);
+    m->chain_batch = swin_chain_images(m, B);
+    if (const int cb = m->chain_batch) {
+        size_t one = 0;       // chain c at offset c * one of the same bytes
+        for (int c = 0; c < m->chains_on; ++c) one = swin_carve(m, m->chain[c], cb, (char*)ws + (size_t)c * one);
         for (int k = 0; k + 1 < m->chains_on; ++k)
             if (!m->side[k]) HIPCHK(hipStreamCreateWithFlags(&m->side[k], hipStreamNonBlocking));
         if (!m->ev_fork) HIPCHK(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
@@ -1656,20 +1656,22 @@ int vl_swin_set_workspace(vl_swin* m, void* ws, size_t bytes) {
     return VL_OK;
 }
 
-static int swin_forward(vl_swin* m, const float* x, int B, int normalise, hipStream_t s) {
-    if (B <= 0 || B > m->max_batch) return vl_fail(VL_ERR_STATE, "batch %d exceeds planned workspace (%d)", B, m->max_batch);
+static int swin_forward(vl_swin* m, SwinWs& w, const float* x, int B, int normalise, hipStream_t s) {
+    if (B <= 0 || B > w.max_batch) return vl_fail(VL_ERR_STATE, "batch %d exceeds planned workspace (%d)", B, w.max_batch);
     const int L0 = m->G0 * m->G0, PK = 3 * m->P * m->P;
     if (m->f16 && m->dirty) swin16_commit(m, s);
     // patch embedding: Conv2d(3, E, k = s = P) as a GEMM over gathered patches, then LayerNorm (SwinEmbeddings)
     if (m->f16) {   // K-tail heads of the unpadded stages' GEMM A operands (zero_tails_kernel)
             TailPtrs tp; tp.n = 0;
-            for (SStage& st : m->stages) {
+            for (int i = 0; i < 4; ++i) {
+                const SStage& st = m->stages[i];
+                const SStageWs& sw = w.st[i];
                 const int64_t Mi = (int64_t)B * st.H * st.H;
-                if (st.LC < st.CP) { tp.p[tp.n++] = st.h16b + Mi * st.LC; tp.p[tp.n++] = st.ctx16 + Mi * st.LC; tp.p[tp.n++] = st.gh16 + Mi * st.LC; }
-                if (st.L3 < st.C3P) tp.p[tp.n++] = st.dqkv16 + Mi * st.L3;
+                if (st.LC < st.CP) { tp.p[tp.n++] = sw.h16b + Mi * st.LC; tp.p[tp.n++] = sw.ctx16 + Mi * st.LC; tp.p[tp.n++] = sw.gh16 + Mi * st.LC; }
+                if (st.L3 < st.C3P) tp.p[tp.n++] = sw.dqkv16 + Mi * st.L3;
             }
             if (m->pe16) {      // patches (48 of the 64-deep K tile)
-                tp.p[tp.n++] = m->patches16 + (int64_t)B * L0 * PK;
+                tp.p[tp.n++] = w.patches16 + (int64_t)B * L0 * PK;
                 // (the embedding gradient is staged in stage 1's h16b -- never a GEMM result, so its pad rows hold nothing but these zeros)
             }
             if (tp.n) hipLaunchKernelGGL(zero_tails_kernel, dim3(tp.n), dim3(64), 0, s, tp);
@@ -1677,36 +1679,37 @@ static int swin_forward(vl_swin* m, const float* x, int B, int normalise, hipStr
     if (m->pe16) {
         // 16-bit patch embedding: h16 patches [B L0][48] (K tail of the 64-deep tile read from the next row against zero weight
         // columns), projection on the streaming GEMM, h16 result of width E
-        hipLaunchKernelGGL(patch_gather16_p4_kernel, dim3(nblk((int64_t)B * L0 * 6, 256, 8192)), dim3(256), 0, s, x, m->patches16, B, m->S, m->G0,
+        hipLaunchKernelGGL(patch_gather16_p4_kernel, dim3(nblk((int64_t)B * L0 * 6, 256, 8192)), dim3(256), 0, s, x, w.patches16, B, m->S, m->G0,
                            normalise, m->mean[0], m->mean[1], m->mean[2], 1.f / m->stdv[0], 1.f / m->stdv[1], 1.f / m->stdv[2]);
-        GemmArgs ge = ga(m->patches16, PK, m->Wpe16, 64, 64, (int)round_up((int64_t)B * L0, 128), 128);
-        ge.Mvalid = B * L0; ge.bias = m->bpe16; ge.C = m->emb16; ge.ldc = m->E; ge.n_store = m->E; ge.n_algo = m->E;
+        GemmArgs ge = ga(w.patches16, PK, m->Wpe16, 64, 64, (int)round_up((int64_t)B * L0, 128), 128);
+        ge.Mvalid = B * L0; ge.bias = m->bpe16; ge.C = w.emb16; ge.ldc = m->E; ge.n_store = m->E; ge.n_algo = m->E;
         launch_gemm(ge, EPI_STORE_H16, 128, s);
     } else {
-    k_patch_gather_f32(x, m->patches, B, m->S, m->P, normalise, m->mean, m->stdv, s);
-    GemmF32 g = gm(m->patches, PK, m->Wpe, PK, 0, B * L0, m->E, PK, m->emb, m->E);
+    k_patch_gather_f32(x, w.patches, B, m->S, m->P, normalise, m->mean, m->stdv, s);
+    GemmF32 g = gm(w.patches, PK, m->Wpe, PK, 0, B * L0, m->E, PK, w.emb, m->E);
     g.bias = m->bpe;
     k_gemm_f32(g, s);
     }
     if (m->f16) {
         // ---- 16-bit path (round 5: h16 residual streams; the embedding LayerNorm's output IS the stream of stage 1) ----
-        if (m->pe16) sw_ln_fwd16<false>(m->emb16, m->E, nullptr, 0, nullptr, 0, m->stages[0].blocks[0].xa16, m->E, m->emean, m->erstd, m->eg,
+        if (m->pe16) sw_ln_fwd16<false>(w.emb16, m->E, nullptr, 0, nullptr, 0, w.st[0].blocks[0].xa16, m->E, w.emean, w.erstd, m->eg,
                                         m->eb, B * L0, m->E, m->cfg.ln_eps, m->err_flag, s);
         else
-        sw_ln_fwd16<true>(m->emb, m->E, nullptr, 0, nullptr, 0, m->stages[0].blocks[0].xa16, m->E, m->emean, m->erstd, m->eg, m->eb,
+        sw_ln_fwd16<true>(w.emb, m->E, nullptr, 0, nullptr, 0, w.st[0].blocks[0].xa16, m->E, w.emean, w.erstd, m->eg, m->eb,
                           B * L0, m->E, m->cfg.ln_eps, m->err_flag, s);
         for (int i = 0; i < 4; ++i) {
-            SStage& st = m->stages[i];
+            const SStage& st = m->stages[i];
+            SStageWs& sw = w.st[i];
             const int Cs = st.C, Hs = st.H, M = B * Hs * Hs;
-            // the stream leaves a block as {bk.xb16, st.delta16}: the next LayerNorm adds them
+            // the stream leaves a block as {bw.xb16, sw.delta16}: the next LayerNorm adds them
             for (int bi = 0; bi < st.depth; ++bi) {
                 const int shift = (bi & 1) && Hs > WS ? WS / 2 : 0;          // SwinLayer: no shift when the window covers the map
-                swin16_block_fwd(m, st, st.blocks[bi], bi ? st.blocks[bi - 1].xb16 : nullptr, bi > 0, B, shift, s);
+                swin16_block_fwd(m, st, sw, st.blocks[bi], sw.blocks[bi], bi ? sw.blocks[bi - 1].xb16 : nullptr, bi > 0, B, shift, s);
             }
-            const SBlock& last = st.blocks[st.depth - 1];
+            const SBlockWs& last = sw.blocks[st.depth - 1];
             if (i == 3) {
                 // stage output x' = round16(xb + delta) -> xlast16, and the final LayerNorm over every token in the same pass
-                sw_ln_fwd16<false>(last.xb16, Cs, st.delta16, st.LD, m->xlast16, Cs, m->hfin16, Cs, m->fmean, m->frstd, m->fg, m->fb, M, Cs,
+                sw_ln_fwd16<false>(last.xb16, Cs, sw.delta16, st.LD, w.xlast16, Cs, w.hfin16, Cs, w.fmean, w.frstd, m->fg, m->fb, M, Cs,
                                    m->cfg.ln_eps, m->err_flag, s);
                 break;
             }
@@ -1716,161 +1719,166 @@ static int swin_forward(vl_swin* m, const float* x, int B, int normalise, hipStr
             merge_dispatch(Cs, [&](auto nv, auto gl) {
                 constexpr int NV = decltype(nv)::value, GL = decltype(gl)::value;
                 hipLaunchKernelGGL((merge_ln_fwd16_kernel<NV, GL>), dim3((M / 4 + 4 * (64 / GL) - 1) / (4 * (64 / GL))), dim3(256), 0, s,
-                                   last.xb16, st.delta16, st.LD, st.mg16, st.mmean, st.mrstd, st.mg_g, st.mg_b, B, Hs, Hs, Cs, m->cfg.ln_eps);
+                                   last.xb16, sw.delta16, st.LD, sw.mg16, sw.mmean, sw.mrstd, st.mg_g, st.mg_b, B, Hs, Hs, Cs, m->cfg.ln_eps);
             });
-            GemmArgs g16a = ga(st.mg16, 4 * Cs, st.Wred16, 4 * Cs, 4 * Cs, Mq, N2);
-            g16a.Mvalid = M / 4; g16a.C = m->stages[i + 1].blocks[0].xa16; g16a.ldc = 2 * Cs; g16a.n_store = N2 > 2 * Cs ? 2 * Cs : 0;
+            GemmArgs g16a = ga(sw.mg16, 4 * Cs, st.Wred16, 4 * Cs, 4 * Cs, Mq, N2);
+            g16a.Mvalid = M / 4; g16a.C = w.st[i + 1].blocks[0].xa16; g16a.ldc = 2 * Cs; g16a.n_store = N2 > 2 * Cs ? 2 * Cs : 0;
             launch_gemm(g16a, EPI_STORE_H16, 128, s);
         }
         const int Cl = m->E << 3, Ll = m->stages[3].H * m->stages[3].H;
-        hipLaunchKernelGGL(mean_pool16_kernel, dim3(nblk((int64_t)B * Cl, 256, 1 << 30)), dim3(256), 0, s, m->hfin16, m->pooled, B, Ll, Cl);
-        hipLaunchKernelGGL(cls_fwd_kernel, dim3(nblk((int64_t)B * m->C, 4, 1 << 30)), dim3(256), 0, s, m->pooled, m->Wc, m->bc, m->logits, B,
+        hipLaunchKernelGGL(mean_pool16_kernel, dim3(nblk((int64_t)B * Cl, 256, 1 << 30)), dim3(256), 0, s, w.hfin16, w.pooled, B, Ll, Cl);
+        hipLaunchKernelGGL(cls_fwd_kernel, dim3(nblk((int64_t)B * m->C, 4, 1 << 30)), dim3(256), 0, s, w.pooled, m->Wc, m->bc, w.logits, B,
                            m->C, Cl);
-        m->cur_B = B; m->cur_norm = normalise; m->have_loss = 0;
+        w.cur_B = B; w.cur_norm = normalise; w.have_loss = 0;
         return VL_OK;
     }
-    k_ln_fwd_f32(m->emb, m->stages[0].blocks[0].xa, m->emean, m->erstd, m->eg, m->eb, B * L0, m->E, m->cfg.ln_eps, s);
+    k_ln_fwd_f32(w.emb, w.st[0].blocks[0].xa, w.emean, w.erstd, m->eg, m->eb, B * L0, m->E, m->cfg.ln_eps, s);
     for (int i = 0; i < 4; ++i) {
-        SStage& st = m->stages[i];
+        const SStage& st = m->stages[i];
+        SStageWs& sw = w.st[i];
         const int Cs = st.C, Hs = st.H, M = B * Hs * Hs;
         const int nW = (Hs / WS) * (Hs / WS);
         for (int bi = 0; bi < st.depth; ++bi) {
-            SBlock& bk = st.blocks[bi];
+            const SBlock& bk = st.blocks[bi];
+            SBlockWs& bw = sw.blocks[bi];
             const int shift = (bi & 1) && Hs > WS ? WS / 2 : 0;          // SwinLayer: no shift when the window covers the map
-            float* xout = bi + 1 < st.depth ? st.blocks[bi + 1].xa : (i < 3 ? m->dbig : m->xlast);
-            k_ln_fwd_f32(bk.xa, m->h, bk.mean1, bk.rstd1, bk.ln1_g, bk.ln1_b, M, Cs, m->cfg.ln_eps, s);
-            lin_fwd(m, bk.qkv, m->h, M, bk.qkvbuf, nullptr, s);
+            float* xout = bi + 1 < st.depth ? sw.blocks[bi + 1].xa : (i < 3 ? w.dbig : w.xlast);
+            k_ln_fwd_f32(bw.xa, w.h, bw.mean1, bw.rstd1, bk.ln1_g, bk.ln1_b, M, Cs, m->cfg.ln_eps, s);
+            lin_fwd(m, w, bk.qkv, w.h, M, bw.qkvbuf, nullptr, s);
             if (g_poison_lds) vl_poison_lds(s);      // test hook (prof.h): the window kernels keep K / V / Q / dO of a window in LDS
-            hipLaunchKernelGGL(win_attn_fwd_kernel, dim3(nblk((int64_t)B * nW * st.heads, 4, 1 << 30)), dim3(256), 0, s, bk.qkvbuf,
-                               bk.table, bk.ctx, bk.lse, B, Hs, Hs, Cs, st.heads, shift);
-            lin_fwd(m, bk.o, bk.ctx, M, bk.xb, bk.xa, s);
-            k_ln_fwd_f32(bk.xb, m->h, bk.mean2, bk.rstd2, bk.ln2_g, bk.ln2_b, M, Cs, m->cfg.ln_eps, s);
-            lin_fwd(m, bk.fc1, m->h, M, bk.z, nullptr, s);
-            k_gelu_fwd_f32(bk.z, m->a, (int64_t)M * 4 * Cs, s);
-            lin_fwd(m, bk.fc2, m->a, M, xout, bk.xb, s);
+            hipLaunchKernelGGL(win_attn_fwd_kernel, dim3(nblk((int64_t)B * nW * st.heads, 4, 1 << 30)), dim3(256), 0, s, bw.qkvbuf,
+                               bk.table, bw.ctx, bw.lse, B, Hs, Hs, Cs, st.heads, shift);
+            lin_fwd(m, w, bk.o, bw.ctx, M, bw.xb, bw.xa, s);
+            k_ln_fwd_f32(bw.xb, w.h, bw.mean2, bw.rstd2, bk.ln2_g, bk.ln2_b, M, Cs, m->cfg.ln_eps, s);
+            lin_fwd(m, w, bk.fc1, w.h, M, bw.z, nullptr, s);
+            k_gelu_fwd_f32(bw.z, w.a, (int64_t)M * 4 * Cs, s);
+            lin_fwd(m, w, bk.fc2, w.a, M, xout, bw.xb, s);
         }
         if (i < 3) {        // SwinPatchMerging: 2x2 neighbourhood -> 4C, LayerNorm, Linear(4C -> 2C, no bias)
-            hipLaunchKernelGGL(merge_gather_kernel, dim3(nblk((int64_t)M * Cs, 256, 8192)), dim3(256), 0, s, m->dbig, st.mg, B, Hs,
+            hipLaunchKernelGGL(merge_gather_kernel, dim3(nblk((int64_t)M * Cs, 256, 8192)), dim3(256), 0, s, w.dbig, sw.mg, B, Hs,
                                Hs, Cs, 0);
-            k_ln_fwd_f32(st.mg, m->h, st.mmean, st.mrstd, st.mg_g, st.mg_b, M / 4, 4 * Cs, m->cfg.ln_eps, s);
-            k_gemm_f32(gm(m->h, 4 * Cs, st.Wred, 4 * Cs, 0, M / 4, 2 * Cs, 4 * Cs, m->stages[i + 1].blocks[0].xa, 2 * Cs), s);
+            k_ln_fwd_f32(sw.mg, w.h, sw.mmean, sw.mrstd, st.mg_g, st.mg_b, M / 4, 4 * Cs, m->cfg.ln_eps, s);
+            k_gemm_f32(gm(w.h, 4 * Cs, st.Wred, 4 * Cs, 0, M / 4, 2 * Cs, 4 * Cs, w.st[i + 1].blocks[0].xa, 2 * Cs), s);
         }
     }
     // final LayerNorm over every token, mean pool, classifier (SwinModel.pooler + SwinForImageClassification.classifier)
     const int Cl = m->E << 3, Ll = m->stages[3].H * m->stages[3].H;
-    k_ln_fwd_f32(m->xlast, m->hfin, m->fmean, m->frstd, m->fg, m->fb, B * Ll, Cl, m->cfg.ln_eps, s);
-    hipLaunchKernelGGL(mean_pool_kernel, dim3(nblk((int64_t)B * Cl, 256, 1 << 30)), dim3(256), 0, s, m->hfin, m->pooled, B, Ll, Cl);
-    hipLaunchKernelGGL(cls_fwd_kernel, dim3(nblk((int64_t)B * m->C, 4, 1 << 30)), dim3(256), 0, s, m->pooled, m->Wc, m->bc, m->logits, B,
+    k_ln_fwd_f32(w.xlast, w.hfin, w.fmean, w.frstd, m->fg, m->fb, B * Ll, Cl, m->cfg.ln_eps, s);
+    hipLaunchKernelGGL(mean_pool_kernel, dim3(nblk((int64_t)B * Cl, 256, 1 << 30)), dim3(256), 0, s, w.hfin, w.pooled, B, Ll, Cl);
+    hipLaunchKernelGGL(cls_fwd_kernel, dim3(nblk((int64_t)B * m->C, 4, 1 << 30)), dim3(256), 0, s, w.pooled, m->Wc, m->bc, w.logits, B,
                        m->C, Cl);
-    m->cur_B = B; m->cur_norm = normalise; m->have_loss = 0;
+    w.cur_B = B; w.cur_norm = normalise; w.have_loss = 0;
     return VL_OK;
 }
 
-static int swin_backward(vl_swin* m, float* grad_x, hipStream_t s) {
-    if (!m->have_loss) return vl_fail(VL_ERR_STATE, "backward before vl_swin_loss_ce");
-    const int B = m->cur_B;
+static int swin_backward(const vl_swin* m, SwinWs& w, float* grad_x, hipStream_t s) {
+    if (!w.have_loss) return vl_fail(VL_ERR_STATE, "backward before vl_swin_loss_ce");
+    const int B = w.cur_B;
     const int Cl = m->E << 3, Ll = m->stages[3].H * m->stages[3].H;
     // head: d(pooled) = dlogits Wc ; d(hfin)[b, t] = d(pooled)[b] / L ; LayerNorm backward
-    const float* dlog = m->dlogits;
+    const float* dlog = w.dlogits;
     if (m->f16) {
         // per-image power-of-two scale: the largest |dLoss/dlogits| of an image lands in [2^9, 2^10) (as the ViT 16-bit path;
         // the chain is linear and per image, so it is exact up to under / overflow and is undone at the pixels)
-        k_grad_scale(m->dlogits, B, m->C, 0, m->gscale, m->inv_gscale, s);
-        hipLaunchKernelGGL(scale_rows_kernel, dim3(nblk((int64_t)B * m->C, 256, 1024)), dim3(256), 0, s, m->dlogits, m->gscale, m->dlogits_s, B, (int64_t)m->C);
-        dlog = m->dlogits_s;
+        k_grad_scale(w.dlogits, B, m->C, 0, w.gscale, w.inv_gscale, s);
+        hipLaunchKernelGGL(scale_rows_kernel, dim3(nblk((int64_t)B * m->C, 256, 1024)), dim3(256), 0, s, w.dlogits, w.gscale, w.dlogits_s, B, (int64_t)m->C);
+        dlog = w.dlogits_s;
     }
-    hipLaunchKernelGGL(cls_bwd_kernel, dim3(nblk((int64_t)B * Cl, 256, 1 << 30)), dim3(256), 0, s, dlog, m->Wc, m->dpooled, B, m->C, Cl);
+    hipLaunchKernelGGL(cls_bwd_kernel, dim3(nblk((int64_t)B * Cl, 256, 1 << 30)), dim3(256), 0, s, dlog, m->Wc, w.dpooled, B, m->C, Cl);
     if (m->f16) {
-        // ---- 16-bit path: ONE h16 gradient stream per stage (st.gh16, row stride st.LC), updated in place by every LayerNorm
+        // ---- 16-bit path: ONE h16 gradient stream per stage (sw.gh16, row stride st.LC), updated in place by every LayerNorm
         // backward and read as the A operand of the dgrad GEMMs (round 5; the fp32 stream + h16 shadow of round 3 are gone) ----
-        hipLaunchKernelGGL(mean_pool_bwd16_kernel, dim3(nblk((int64_t)B * Ll * Cl, 256, 1 << 30)), dim3(256), 0, s, m->dpooled, m->dhfin16, B, Ll, Cl);
-        sw_ln_bwd16<false, false>(m->dhfin16, Cl, m->xlast16, Cl, m->fmean, m->frstd, m->fg, nullptr, m->stages[3].gh16, m->stages[3].LC,
+        hipLaunchKernelGGL(mean_pool_bwd16_kernel, dim3(nblk((int64_t)B * Ll * Cl, 256, 1 << 30)), dim3(256), 0, s, w.dpooled, w.dhfin16, B, Ll, Cl);
+        sw_ln_bwd16<false, false>(w.dhfin16, Cl, w.xlast16, Cl, w.fmean, w.frstd, m->fg, nullptr, w.st[3].gh16, m->stages[3].LC,
                                   B * Ll, Cl, m->err_flag, s);
         for (int i = 3; i >= 0; --i) {
-            SStage& st = m->stages[i];
+            const SStage& st = m->stages[i];
+            SStageWs& sw = w.st[i];
             const int Cs = st.C, Hs = st.H, M = B * Hs * Hs;
             if (i < 3) {
-                // the next stage's gradient stream [M/4, 2C] -> reduction dgrad (h16 result in st.mg16, free in the backward) ->
-                // LayerNorm(4C) backward with x gathered again from {xb16, delta16}, un-merged on the way out into st.gh16
+                // the next stage's gradient stream [M/4, 2C] -> reduction dgrad (h16 result in sw.mg16, free in the backward) ->
+                // LayerNorm(4C) backward with x gathered again from {xb16, delta16}, un-merged on the way out into sw.gh16
                 const SStage& nx = m->stages[i + 1];
                 const int Mq = (int)round_up(M / 4, 128);
-                GemmArgs g16a = ga(nx.gh16, nx.LC, st.WredT16, 2 * Cs, 2 * Cs, Mq, 4 * Cs);
-                g16a.Mvalid = M / 4; g16a.C = st.mg16; g16a.ldc = 4 * Cs;
+                GemmArgs g16a = ga(w.st[i + 1].gh16, nx.LC, st.WredT16, 2 * Cs, 2 * Cs, Mq, 4 * Cs);
+                g16a.Mvalid = M / 4; g16a.C = sw.mg16; g16a.ldc = 4 * Cs;
                 launch_gemm(g16a, EPI_STORE_H16, 128, s);
                 merge_dispatch(Cs, [&](auto nv, auto gl) {
                     constexpr int NV = decltype(nv)::value, GL = decltype(gl)::value;
                     hipLaunchKernelGGL((merge_ln_bwd16_kernel<NV, GL>), dim3((M / 4 + 4 * (64 / GL) - 1) / (4 * (64 / GL))), dim3(256), 0, s,
-                                       st.mg16, st.blocks[st.depth - 1].xb16, st.delta16, st.LD, st.mmean, st.mrstd, st.mg_g, st.gh16,
+                                       sw.mg16, sw.blocks[st.depth - 1].xb16, sw.delta16, st.LD, sw.mmean, sw.mrstd, st.mg_g, sw.gh16,
                                        st.LC, B, Hs, Hs, Cs, m->err_flag);
                 });
             }
             for (int bi = st.depth - 1; bi >= 0; --bi) {
                 const int shift = (bi & 1) && Hs > WS ? WS / 2 : 0;
-                swin16_block_bwd(m, st, st.blocks[bi], B, shift, s);
+                swin16_block_bwd(m, st, sw, st.blocks[bi], sw.blocks[bi], B, shift, s);
             }
         }
         if (grad_x) {
             const int L0 = m->G0 * m->G0, PK = 3 * m->P * m->P;
             // embedding LayerNorm backward (x = the fp32 patch-embedding output) -> fp32, then the patch projection's dgrad in fp32
             float is[3];
-            for (int c = 0; c < 3; ++c) is[c] = m->cur_norm ? 1.f / m->stdv[c] : 1.f;
+            for (int c = 0; c < 3; ++c) is[c] = w.cur_norm ? 1.f / m->stdv[c] : 1.f;
             if (m->pe16) {
                 // embedding LayerNorm backward on h16 (its result in stage 1's h16b, free by now), the projection's dgrad on the
                 // streaming GEMM (h16 d(patches) over the forward's patches), then ONE scatter to pixels that also undoes the scale
-                h16* gemb = m->stages[0].h16b;       // (a LayerNorm-output buffer: rows >= M are never written, its K-tail head is zeroed per forward)
-                sw_ln_bwd16<false, false>(m->stages[0].gh16, m->stages[0].LC, m->emb16, m->E, m->emean, m->erstd, m->eg, nullptr, gemb, m->E,
+                h16* gemb = w.st[0].h16b;       // (a LayerNorm-output buffer: rows >= M are never written, its K-tail head is zeroed per forward)
+                sw_ln_bwd16<false, false>(w.st[0].gh16, m->stages[0].LC, w.emb16, m->E, w.emean, w.erstd, m->eg, nullptr, gemb, m->E,
                                           B * L0, m->E, m->err_flag, s);
                 GemmArgs gd = ga(gemb, m->E, m->WpeT16, 128, 128, (int)round_up((int64_t)B * L0, 128), 128);
-                gd.Mvalid = B * L0; gd.C = m->patches16; gd.ldc = PK; gd.n_store = PK; gd.n_algo = PK;
+                gd.Mvalid = B * L0; gd.C = w.patches16; gd.ldc = PK; gd.n_store = PK; gd.n_algo = PK;
                 launch_gemm(gd, EPI_STORE_H16, 128, s);
-                hipLaunchKernelGGL(patch_scatter16_p4_kernel, dim3(nblk((int64_t)B * L0 * 6, 256, 8192)), dim3(256), 0, s, m->patches16, grad_x, B, m->S,
-                                   m->G0, is[0], is[1], is[2], m->inv_gscale, m->err_flag);
+                hipLaunchKernelGGL(patch_scatter16_p4_kernel, dim3(nblk((int64_t)B * L0 * 6, 256, 8192)), dim3(256), 0, s, w.patches16, grad_x, B, m->S,
+                                   m->G0, is[0], is[1], is[2], w.inv_gscale, m->err_flag);
                 return VL_OK;
             }
-            sw_ln_bwd16<true, true>(m->stages[0].gh16, m->stages[0].LC, m->emb, m->E, m->emean, m->erstd, m->eg, nullptr, m->g1, m->E,
+            sw_ln_bwd16<true, true>(w.st[0].gh16, m->stages[0].LC, w.emb, m->E, w.emean, w.erstd, m->eg, nullptr, w.g1, m->E,
                                     B * L0, m->E, m->err_flag, s);
-            k_gemm_f32(gm(m->g1, m->E, m->Wpe, PK, 1, B * L0, PK, m->E, m->patches, PK), s);
-            k_patch_scatter_f32(m->patches, grad_x, B, m->S, m->P, is, s);
+            k_gemm_f32(gm(w.g1, m->E, m->Wpe, PK, 1, B * L0, PK, m->E, w.patches, PK), s);
+            k_patch_scatter_f32(w.patches, grad_x, B, m->S, m->P, is, s);
             // undo the per-image gradient scale
-            hipLaunchKernelGGL(scale_rows_kernel, dim3(8192), dim3(256), 0, s, grad_x, m->inv_gscale, grad_x, B, (int64_t)3 * m->S * m->S);
+            hipLaunchKernelGGL(scale_rows_kernel, dim3(8192), dim3(256), 0, s, grad_x, w.inv_gscale, grad_x, B, (int64_t)3 * m->S * m->S);
         }
         return VL_OK;
     }
-    hipLaunchKernelGGL(mean_pool_bwd_kernel, dim3(nblk((int64_t)B * Ll * Cl, 256, 1 << 30)), dim3(256), 0, s, m->dpooled, m->h, B, Ll, Cl);
-    float *gcur = m->g0, *gnext = m->g1;
-    k_ln_bwd_f32(m->h, m->xlast, m->fmean, m->frstd, m->fg, nullptr, gcur, B * Ll, Cl, s);
+    hipLaunchKernelGGL(mean_pool_bwd_kernel, dim3(nblk((int64_t)B * Ll * Cl, 256, 1 << 30)), dim3(256), 0, s, w.dpooled, w.h, B, Ll, Cl);
+    float *gcur = w.g0, *gnext = w.g1;
+    k_ln_bwd_f32(w.h, w.xlast, w.fmean, w.frstd, m->fg, nullptr, gcur, B * Ll, Cl, s);
     for (int i = 3; i >= 0; --i) {
-        SStage& st = m->stages[i];
+        const SStage& st = m->stages[i];
+        SStageWs& sw = w.st[i];
         const int Cs = st.C, Hs = st.H, M = B * Hs * Hs;
         const int nW = (Hs / WS) * (Hs / WS);
         if (i < 3) {
             // gcur = gradient w.r.t. the next stage's input [M/4, 2C]: reduction dgrad, LayerNorm backward, un-merge
-            k_gemm_f32(gm(gcur, 2 * Cs, st.Wred, 4 * Cs, 1, M / 4, 4 * Cs, 2 * Cs, m->dbig, 4 * Cs), s);
-            k_ln_bwd_f32(m->dbig, st.mg, st.mmean, st.mrstd, st.mg_g, nullptr, m->h, M / 4, 4 * Cs, s);
-            hipLaunchKernelGGL(merge_gather_kernel, dim3(nblk((int64_t)M * Cs, 256, 8192)), dim3(256), 0, s, m->h, gcur, B, Hs, Hs, Cs, 1);
+            k_gemm_f32(gm(gcur, 2 * Cs, st.Wred, 4 * Cs, 1, M / 4, 4 * Cs, 2 * Cs, w.dbig, 4 * Cs), s);
+            k_ln_bwd_f32(w.dbig, sw.mg, sw.mmean, sw.mrstd, st.mg_g, nullptr, w.h, M / 4, 4 * Cs, s);
+            hipLaunchKernelGGL(merge_gather_kernel, dim3(nblk((int64_t)M * Cs, 256, 8192)), dim3(256), 0, s, w.h, gcur, B, Hs, Hs, Cs, 1);
         }
         for (int bi = st.depth - 1; bi >= 0; --bi) {
-            SBlock& bk = st.blocks[bi];
+            const SBlock& bk = st.blocks[bi];
+            SBlockWs& bw = sw.blocks[bi];
             const int shift = (bi & 1) && Hs > WS ? WS / 2 : 0;
-            lin_dgrad(m, bk.fc2, gcur, M, m->dbig, s);                                   // d(a)
-            k_gelu_bwd_f32(m->dbig, bk.z, (int64_t)M * 4 * Cs, s);                       // d(z)
-            lin_dgrad(m, bk.fc1, m->dbig, M, m->h, s);
-            k_ln_bwd_f32(m->h, bk.xb, bk.mean2, bk.rstd2, bk.ln2_g, gcur, gnext, M, Cs, s);
-            lin_dgrad(m, bk.o, gnext, M, m->a, s);                                       // d(ctx)
+            lin_dgrad(m, w, bk.fc2, gcur, M, w.dbig, s);                                   // d(a)
+            k_gelu_bwd_f32(w.dbig, bw.z, (int64_t)M * 4 * Cs, s);                       // d(z)
+            lin_dgrad(m, w, bk.fc1, w.dbig, M, w.h, s);
+            k_ln_bwd_f32(w.h, bw.xb, bw.mean2, bw.rstd2, bk.ln2_g, gcur, gnext, M, Cs, s);
+            lin_dgrad(m, w, bk.o, gnext, M, w.a, s);                                       // d(ctx)
             if (g_poison_lds) vl_poison_lds(s);      // test hook (prof.h): the window kernels keep K / V / Q / dO of a window in LDS
-            hipLaunchKernelGGL(win_attn_bwd_kernel, dim3(nblk((int64_t)B * nW * st.heads, 2, 1 << 30)), dim3(128), 0, s, bk.qkvbuf,
-                               bk.table, bk.ctx, m->a, bk.lse, m->dqkv, B, Hs, Hs, Cs, st.heads, shift);
-            lin_dgrad(m, bk.qkv, m->dqkv, M, m->h, s);
-            k_ln_bwd_f32(m->h, bk.xa, bk.mean1, bk.rstd1, bk.ln1_g, gnext, gcur, M, Cs, s);
+            hipLaunchKernelGGL(win_attn_bwd_kernel, dim3(nblk((int64_t)B * nW * st.heads, 2, 1 << 30)), dim3(128), 0, s, bw.qkvbuf,
+                               bk.table, bw.ctx, w.a, bw.lse, w.dqkv, B, Hs, Hs, Cs, st.heads, shift);
+            lin_dgrad(m, w, bk.qkv, w.dqkv, M, w.h, s);
+            k_ln_bwd_f32(w.h, bw.xa, bw.mean1, bw.rstd1, bk.ln1_g, gnext, gcur, M, Cs, s);
         }
     }
     if (grad_x) {
         const int L0 = m->G0 * m->G0, PK = 3 * m->P * m->P;
-        k_ln_bwd_f32(gcur, m->emb, m->emean, m->erstd, m->eg, nullptr, gnext, B * L0, m->E, s);
-        k_gemm_f32(gm(gnext, m->E, m->Wpe, PK, 1, B * L0, PK, m->E, m->patches, PK), s);
+        k_ln_bwd_f32(gcur, w.emb, w.emean, w.erstd, m->eg, nullptr, gnext, B * L0, m->E, s);
+        k_gemm_f32(gm(gnext, m->E, m->Wpe, PK, 1, B * L0, PK, m->E, w.patches, PK), s);
         float is[3];
-        for (int c = 0; c < 3; ++c) is[c] = m->cur_norm ? 1.f / m->stdv[c] : 1.f;
-        k_patch_scatter_f32(m->patches, grad_x, B, m->S, m->P, is, s);
+        for (int c = 0; c < 3; ++c) is[c] = w.cur_norm ? 1.f / m->stdv[c] : 1.f;
+        k_patch_scatter_f32(w.patches, grad_x, B, m->S, m->P, is, s);
     }
     return VL_OK;
 }
@@ -1897,20 +1905,21 @@ static int swin_launch_ok(const char* what) {
 
 int vl_swin_forward(vl_swin* m, const float* x, int batch, int normalise, float* logits_out, void* stream) {
     if (!m || !x) return vl_fail(VL_ERR_ARG, "null argument");
-    if (m->max_batch <= 0) return vl_fail(VL_ERR_STATE, "no workspace: call vl_swin_plan + vl_swin_set_workspace first");
+    if (m->w.max_batch <= 0) return vl_fail(VL_ERR_STATE, "no workspace: call vl_swin_plan + vl_swin_set_workspace first");
     int rc = swin_check(m);
     if (rc) return rc;
-    if ((rc = swin_forward(m, x, batch, normalise, (hipStream_t)stream))) return rc;
-    if (logits_out) HIPCHK(hipMemcpyAsync(logits_out, m->logits, (size_t)batch * m->C * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if ((rc = swin_forward(m, m->w, x, batch, normalise, (hipStream_t)stream))) return rc;
+    if (logits_out) HIPCHK(hipMemcpyAsync(logits_out, m->w.logits, (size_t)batch * m->C * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return swin_launch_ok("vl_swin_forward");
 }
 
 int vl_swin_loss_ce(vl_swin* m, const int64_t* labels, float* loss_out, void* stream) {
     if (!m || !labels) return vl_fail(VL_ERR_ARG, "null argument");
-    if (!m->cur_B) return vl_fail(VL_ERR_STATE, "vl_swin_loss_ce before vl_swin_forward");
-    k_ce_loss(m->logits, labels, m->cur_B, m->C, m->dlogits, m->loss_img, m->loss, m->err_flag, (hipStream_t)stream);
-    if (loss_out) HIPCHK(hipMemcpyAsync(loss_out, m->loss, sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    m->have_loss = 1;
+    SwinWs& w = m->w;
+    if (!w.cur_B) return vl_fail(VL_ERR_STATE, "vl_swin_loss_ce before vl_swin_forward");
+    k_ce_loss(w.logits, labels, w.cur_B, m->C, w.dlogits, w.loss_img, w.loss, m->err_flag, (hipStream_t)stream);
+    if (loss_out) HIPCHK(hipMemcpyAsync(loss_out, w.loss, sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    w.have_loss = 1;
     return VL_OK;
 }
 
@@ -1918,71 +1927,70 @@ int vl_swin_backward_input(vl_swin* m, float* grad_x_out, void* stream) {
     if (!m || !grad_x_out) return vl_fail(VL_ERR_ARG, "null argument");
     int rc = swin_check(m);
     if (rc) return rc;
-    if ((rc = swin_backward(m, grad_x_out, (hipStream_t)stream))) return rc;
+    if ((rc = swin_backward(m, m->w, grad_x_out, (hipStream_t)stream))) return rc;
     return swin_launch_ok("vl_swin_backward_input");
 }
 
 int vl_swin_pgd_attack(vl_swin* m, const float* x0, const int64_t* labels, int batch, float eps, float alpha, int steps,
                        int random_start, uint64_t seed, float* adv_out, void* stream) {
     if (!m || !x0 || !labels || !adv_out) return vl_fail(VL_ERR_ARG, "bad argument");
-    if (m->max_batch <= 0 || batch <= 0 || batch > m->max_batch) return vl_fail(VL_ERR_STATE, "batch exceeds planned workspace");
+    SwinWs& w = m->w;
+    if (w.max_batch <= 0 || batch <= 0 || batch > w.max_batch) return vl_fail(VL_ERR_STATE, "batch exceeds planned workspace");
     hipStream_t s = (hipStream_t)stream;
     int rc = swin_check(m);
     if (rc) return rc;
     const int64_t n = (int64_t)batch * 3 * m->S * m->S;
     if (m->chain_batch && batch >= m->chain_min && batch >= m->chains_on && steps > 0) {
-        // ---- two half-batch chains (see the handle): images are independent, the halves run on s and on the side stream ----
+        // ---- two half-batch chains (see the handle): images are independent, chain c runs in workspace m->chain[c] on s / a side stream ----
         const int NC = m->chains_on;
         int bsz[vl_swin::MAXCH], first[vl_swin::MAXCH];
         for (int c = 0, at = 0; c < NC; ++c) { bsz[c] = batch / NC + (c < batch % NC ? 1 : 0); first[c] = at; at += bsz[c]; }
         const int64_t img = (int64_t)3 * m->S * m->S;
         if (m->f16 && m->dirty) { swin16_commit(m, s); }
         for (int c = 0; c < NC; ++c) {
-            vl_swin* ch = m->chain[c];
-            ch->dirty = 0; ch->mean[0] = m->mean[0]; ch->mean[1] = m->mean[1]; ch->mean[2] = m->mean[2];
-            ch->stdv[0] = m->stdv[0]; ch->stdv[1] = m->stdv[1]; ch->stdv[2] = m->stdv[2];
-            HIPCHK(hipMemcpyAsync(ch->stage_x0, x0 + first[c] * img, (size_t)bsz[c] * img * sizeof(float), hipMemcpyDeviceToDevice, s));
-            HIPCHK(hipMemcpyAsync(ch->stage_labels, labels + first[c], (size_t)bsz[c] * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+            SwinWs& ch = m->chain[c];
+            HIPCHK(hipMemcpyAsync(ch.stage_x0, x0 + first[c] * img, (size_t)bsz[c] * img * sizeof(float), hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(ch.stage_labels, labels + first[c], (size_t)bsz[c] * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
         }
         // the random start is a function of (seed, element index of the WHOLE batch): drawn once into the caller's buffer
         if (random_start) k_pgd_init(adv_out, x0, eps, 0.f, 1.f, seed, n, s);
         else if (adv_out != x0) HIPCHK(hipMemcpyAsync(adv_out, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
         for (int c = 0; c < NC; ++c)
-            HIPCHK(hipMemcpyAsync(m->chain[c]->stage_adv, adv_out + first[c] * img, (size_t)bsz[c] * img * sizeof(float), hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(m->chain[c].stage_adv, adv_out + first[c] * img, (size_t)bsz[c] * img * sizeof(float), hipMemcpyDeviceToDevice, s));
         HIPCHK(hipEventRecord(m->ev_fork, s));
         for (int c = 1; c < NC; ++c) HIPCHK(hipStreamWaitEvent(m->side[c - 1], m->ev_fork, 0));
         for (int i = 0; i < steps; ++i)
             for (int c = 0; c < NC; ++c) {
-                vl_swin* ch = m->chain[c];
+                SwinWs& ch = m->chain[c];
                 hipStream_t sc = c ? m->side[c - 1] : s;
                 const int64_t nc = (int64_t)bsz[c] * img;
-                if ((rc = swin_forward(ch, ch->stage_adv, bsz[c], 1, sc))) return rc;
-                k_ce_loss(ch->logits, ch->stage_labels, bsz[c], ch->C, ch->dlogits, ch->loss_img, ch->loss, ch->err_flag, sc);
-                ch->have_loss = 1;
-                if ((rc = swin_backward(ch, ch->grad_img, sc))) return rc;
-                k_pgd_step(ch->stage_adv, ch->stage_x0, ch->grad_img, eps, alpha, 0.f, 1.f, nc, sc, ch->err_flag);
+                if ((rc = swin_forward(m, ch, ch.stage_adv, bsz[c], 1, sc))) return rc;
+                k_ce_loss(ch.logits, ch.stage_labels, bsz[c], m->C, ch.dlogits, ch.loss_img, ch.loss, m->err_flag, sc);
+                ch.have_loss = 1;
+                if ((rc = swin_backward(m, ch, ch.grad_img, sc))) return rc;
+                k_pgd_step(ch.stage_adv, ch.stage_x0, ch.grad_img, eps, alpha, 0.f, 1.f, nc, sc, m->err_flag);
             }
         for (int c = 1; c < NC; ++c) {
             HIPCHK(hipEventRecord(m->ev_join, m->side[c - 1]));
             HIPCHK(hipStreamWaitEvent(s, m->ev_join, 0));
         }
         for (int c = 0; c < NC; ++c)
-            HIPCHK(hipMemcpyAsync(adv_out + first[c] * img, m->chain[c]->stage_adv, (size_t)bsz[c] * img * sizeof(float), hipMemcpyDeviceToDevice, s));
-        m->cur_B = 0; m->have_loss = 0;        // the main workspace shares its bytes with the chains: no forward of the whole batch is held
+            HIPCHK(hipMemcpyAsync(adv_out + first[c] * img, m->chain[c].stage_adv, (size_t)bsz[c] * img * sizeof(float), hipMemcpyDeviceToDevice, s));
+        w.cur_B = 0; w.have_loss = 0;        // the main workspace shares its bytes with the chains: no forward of the whole batch is held
         return swin_launch_ok("vl_swin_pgd_attack");
     }
-    HIPCHK(hipMemcpyAsync(m->stage_x0, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(m->stage_labels, labels, (size_t)batch * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    if (random_start) k_pgd_init(m->stage_adv, m->stage_x0, eps, 0.f, 1.f, seed, n, s);
-    else HIPCHK(hipMemcpyAsync(m->stage_adv, m->stage_x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(w.stage_x0, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(w.stage_labels, labels, (size_t)batch * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    if (random_start) k_pgd_init(w.stage_adv, w.stage_x0, eps, 0.f, 1.f, seed, n, s);
+    else HIPCHK(hipMemcpyAsync(w.stage_adv, w.stage_x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     for (int i = 0; i < steps; ++i) {
-        if ((rc = swin_forward(m, m->stage_adv, batch, 1, s))) return rc;
-        k_ce_loss(m->logits, m->stage_labels, batch, m->C, m->dlogits, m->loss_img, m->loss, m->err_flag, s);
-        m->have_loss = 1;
-        if ((rc = swin_backward(m, m->grad_img, s))) return rc;
-        k_pgd_step(m->stage_adv, m->stage_x0, m->grad_img, eps, alpha, 0.f, 1.f, n, s, m->err_flag);
+        if ((rc = swin_forward(m, w, w.stage_adv, batch, 1, s))) return rc;
+        k_ce_loss(w.logits, w.stage_labels, batch, m->C, w.dlogits, w.loss_img, w.loss, m->err_flag, s);
+        w.have_loss = 1;
+        if ((rc = swin_backward(m, w, w.grad_img, s))) return rc;
+        k_pgd_step(w.stage_adv, w.stage_x0, w.grad_img, eps, alpha, 0.f, 1.f, n, s, m->err_flag);
     }
-    HIPCHK(hipMemcpyAsync(adv_out, m->stage_adv, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(adv_out, w.stage_adv, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     return swin_launch_ok("vl_swin_pgd_attack");
 }
 

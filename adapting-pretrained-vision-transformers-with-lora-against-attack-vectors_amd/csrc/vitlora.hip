@@ -103,13 +103,17 @@ int fused_down(const vl_model* m, const Linear& ln) {
 // same for the forward: t = h Ad^T out of the LayerNorm that writes h (not with LoRA dropout: the branch then reads
 // dropout(h)).  Only r * modules <= 8 (e.g. r = 4 on q, v): with 24 columns (r = 8 on q, k, v) the 144 registers of
 // P cost the LayerNorm more (+1.1 ms per PGD iteration) than the skinny GEMM it replaces (0.3 ms) -- measured.
-int fused_down_fwd(const vl_model* m, const Linear& ln) {
-    if (m->cfg.lora_merged || !ln.kext || ln.slots.empty() || ln.kext != 64 || ln.in != m->D || vl_drop_on(m)) return 0;
+int fused_down_fwd(const vl_model* m, const Pass& p, const Linear& ln) {
+    if (m->cfg.lora_merged || !ln.kext || ln.slots.empty() || ln.kext != 64 || ln.in != m->D || vl_drop_on(m, p)) return 0;
     const int nc = ext_cols(m, ln);
     return nc <= 8 ? 1 : 0;
 }
 
-
+// GEMM rows of a batch of B images: token rows are padded to a multiple of 256 on the 16-bit path (round 4): the 256-row GEMM then
+// never needs a second, 128-row launch for a leftover half tile -- at batch 64 / 32 (SURVEY 8e's per-GPU shares) that launch was one
+// full tile time for 3 tiles; patch rows to the 128-row tile
+int64_t pad_rows(const vl_model* m, int B) { return round_up((int64_t)B * m->T, m->f32 ? 128 : 256); }
+int64_t pad_patch_rows(const vl_model* m, int B) { return round_up((int64_t)B * m->NP, 128); }
 
 // per-image persistent attention kernels: when the batch fills the chip (one workgroup per image), or forced by
 // VITLORA_ATTN_IMG = 1 / 0 (tests exercise both forms at small batches)
@@ -128,20 +132,21 @@ int down_min_k(const vl_model* m, int Mpad) { return Mpad <= m->small_m_rows ? 7
 
 // y = x W^T (+ LoRA) with epilogue; `t` receives the LoRA down projection when fused.
 // stream_id = layer*4 + projection: names the dropout mask of this projection's LoRA branch input.
-// t_ready: the LayerNorm that produced x already wrote t (fused_down_fwd below).
-void linear_fwd(vl_model* m, const Linear& ln, const h16* x, h16* t, int Mpad, GemmArgs g, int epi, hipStream_t s,
-                uint32_t stream_id, bool t_ready = false) {
+// t_ready: the LayerNorm that produced x already wrote t (fused_down_fwd above).
+// Mpad rows are computed, Mvalid of them may be stored (B * T; B on the compact CLS-row buffers); p: the pass x belongs to.
+void linear_fwd(const vl_model* m, const Pass& p, const Linear& ln, const h16* x, h16* t, int Mpad, int Mvalid, GemmArgs g, int epi,
+                hipStream_t s, uint32_t stream_id, bool t_ready = false) {
     g.A1 = x; g.lda1 = ln.in; g.W1 = ln.W; g.ldw1 = ln.in; g.K1 = ln.in;
     g.M = Mpad; g.N = ln.out; g.bias = ln.bias;
-    g.Mvalid = m->cur_M;
+    g.Mvalid = Mvalid;
     if (ln.kext && !m->cfg.lora_merged) {
         const h16* xb = x;                  // LoRA branch input: dropout(x) in train mode (peft Linear.forward)
-        if (vl_drop_on(m)) {
-            k_dropout(x, m->ws.xd, (int64_t)m->cur_M * ln.in, m->drop_seed, stream_id, m->cfg.lora_dropout, s);
-            xb = m->ws.xd;
+        if (vl_drop_on(m, p)) {
+            k_dropout(x, p.ws.xd, (int64_t)Mvalid * ln.in, m->drop_seed, stream_id, m->cfg.lora_dropout, s);
+            xb = p.ws.xd;
         }
         GemmArgs d = gemm_args(xb, ln.in, ln.Ad, ln.in, ln.in, Mpad, ln.kext);
-        d.Mvalid = m->cur_M; d.n_algo = m->r * (int)ln.slots.size();
+        d.Mvalid = Mvalid; d.n_algo = m->r * (int)ln.slots.size();
         g.k2_algo = m->r;      // each output column sees r LoRA columns
         g.k2_used = ext_cols(m, ln);
         d.C = t; d.ldc = ln.kext;
@@ -164,22 +169,21 @@ void linear_fwd(vl_model* m, const Linear& ln, const h16* x, h16* t, int Mpad, G
 }
 
 // dx = dy W (+ LoRA) with epilogue; `u` receives dy B.
-// u_ready: the kernel that produced dy already wrote u (fused_down below).
-void linear_dgrad(vl_model* m, const Linear& ln, const h16* dy, h16* u, int Mpad, GemmArgs g, int epi, hipStream_t s,
-                  uint32_t stream_id, bool u_ready = false) {
+// u_ready: the kernel that produced dy already wrote u (fused_down above).  Mpad / Mvalid / p as in linear_fwd.
+void linear_dgrad(const vl_model* m, const Pass& p, const Linear& ln, const h16* dy, h16* u, int Mpad, int Mvalid, GemmArgs g, int epi,
+                  hipStream_t s, uint32_t stream_id, bool u_ready = false) {
     g.A1 = dy; g.lda1 = ln.out; g.W1 = ln.WT; g.ldw1 = ln.out; g.K1 = ln.out;
     g.M = Mpad; g.N = ln.in; g.bias = nullptr;
-    g.Mvalid = m->cur_M;
+    g.Mvalid = Mvalid;
     if (ln.kext && !m->cfg.lora_merged) {
         GemmArgs d = gemm_args(dy, ln.out, ln.Bd, ln.out, ln.out, Mpad, ln.kext);
         // u = dy B: each of the r*slots columns sums over its own module's `out` rows only
-        d.Mvalid = m->cur_M; d.n_algo = m->r; 
+        d.Mvalid = Mvalid; d.n_algo = m->r;
         d.C = u; d.ldc = ln.kext;
         // u inside the dgrad GEMM itself (the ping-pong kernel computes it from the dy tiles it streams through LDS: gemm_pp.hip,
         // ND > 0) when no producer of dy delivered it: deep products always, shallow ones at small batches, where a separate
         // skinny launch is pure latency (17 - 22 us for 6 - 12 k rows)
-        bool fused = false;
-        if (!u_ready && !vl_drop_on(m) && ln.out >= down_min_k(m, Mpad) && ln.kext == 64 && epi == EPI_STORE_H16) {
+        if (!u_ready && !vl_drop_on(m, p) && ln.out >= down_min_k(m, Mpad) && ln.kext == 64 && epi == EPI_STORE_H16) {
             GemmArgs f = g;
             f.k2_algo = m->r * (int)ln.slots.size();
             f.k2_used = ext_cols(m, ln);
@@ -188,17 +192,16 @@ void linear_dgrad(vl_model* m, const Linear& ln, const h16* dy, h16* u, int Mpad
             f.down_groups = ext_cols(m, ln) <= 16 ? 1 : ext_cols(m, ln) <= 32 ? 2 : 0;
             if (f.down_groups && gemm_pp_fuses_down(f, epi)) { f.A2 = nullptr; launch_gemm(f, epi, 128, s); return; }
         }
-        (void)fused;
         if (!u_ready) launch_gemm(d, EPI_STORE_H16, 64, s);
-        if (vl_drop_on(m)) {
+        if (vl_drop_on(m, p)) {
             // the LoRA branch saw dropout(x): d(x) = dy W + mask * (u (sA)), then the caller's epilogue factor.
             // two launches: the frozen part into a temporary, then the masked rank-r part on top of it.
             GemmArgs main = g;
-            main.C = m->ws.xd; main.ldc = ln.in; main.R = nullptr; main.C2 = nullptr;
+            main.C = p.ws.xd; main.ldc = ln.in; main.R = nullptr; main.C2 = nullptr;
             launch_gemm(main, EPI_STORE_H16, 128, s);
             GemmArgs lo = gemm_args(u, ln.kext, ln.Au, ln.kext, ln.kext, Mpad, ln.in);
-            lo.Mvalid = m->cur_M; lo.k2_algo = 0;
-            lo.C = g.C; lo.ldc = g.ldc; lo.R = m->ws.xd; lo.ldr = ln.in;
+            lo.Mvalid = Mvalid; lo.k2_algo = 0;
+            lo.C = g.C; lo.ldc = g.ldc; lo.R = p.ws.xd; lo.ldr = ln.in;
             if (epi == EPI_GELU_BWD) { lo.G = (const h16*)g.R; lo.ldg = g.ldr; }
             lo.drop_seed = m->drop_seed; lo.drop_stream = stream_id; lo.drop_p = m->cfg.lora_dropout;
             lo.drop_inv_keep = 1.f / (1.f - m->cfg.lora_dropout);
@@ -255,6 +258,18 @@ bool capturing(hipStream_t s) {
     return st != hipStreamCaptureStatusNone;
 }
 
+// runs fn(c, half pass c, its stream) for both half passes -- chain 0 on `s`, chain 1 on the side stream -- between the fork and
+// the join event; returns the first failure
+template <typename F>
+int on_both_halves(vl_model* m, hipStream_t s, F fn) {
+    HIPCHK(hipEventRecord(m->ev_fork, s));
+    HIPCHK(hipStreamWaitEvent(m->side_stream, m->ev_fork, 0));
+    const int rc0 = fn(0, m->half[0], s), rc1 = fn(1, m->half[1], m->side_stream);
+    HIPCHK(hipEventRecord(m->ev_join, m->side_stream));
+    HIPCHK(hipStreamWaitEvent(s, m->ev_join, 0));
+    return rc0 ? rc0 : rc1;
+}
+
 // the three switches that are neither a flag nor an integer (every other one goes through env.h)
 // VITLORA_RESID: "ln" = 0, "o" = 1, anything else or unset = 2 (vl_model::resid_epi)
 int env_resid() { const char* e = getenv("VITLORA_RESID"); return !e ? 2 : !strcmp(e, "ln") ? 0 : !strcmp(e, "o") ? 1 : 2; }
@@ -265,7 +280,7 @@ const char* env_graph_dump() { const char* e = getenv("VITLORA_GRAPH_DUMP"); ret
 
 }  // namespace
 
-bool vl_drop_on(const vl_model* m) { return m->cur_train && m->r && m->cfg.lora_dropout > 0.f; }
+bool vl_drop_on(const vl_model* m, const Pass& p) { return p.train && m->r && m->cfg.lora_dropout > 0.f; }
 
 extern "C" {
 
@@ -564,18 +579,18 @@ int vl_merge_weight(vl_model* m, int layer, uint32_t target, const float* W_in, 
 }
 
 // ---- workspace -------------------------------------------------------------------------------
-static size_t carve(vl_model* m, int B, int train, char* base) {
-    Workspace& w = m->ws;
+// Lays the activations of up to B images out from `base` into `w` and returns the bytes they take.  base == nullptr: a size
+// query -- the pointers of `w` come out null and w.max_batch = 0 (carve_bytes below hands it a throw-away Workspace).
+static size_t carve(const vl_model* m, Workspace& w, int B, int train, char* base) {
     const int D = m->D, L = m->L, MLP = m->MLP;
-    // token rows are padded to a multiple of 256 on the 16-bit path (round 4): the 256-row GEMM then never needs a second, 128-row
-    // launch for a leftover half tile -- at batch 64 / 32 (SURVEY 8e's per-GPU shares) that launch was one full tile time for 3 tiles
-    const int64_t Mpad = round_up((int64_t)B * m->T, m->f32 ? 128 : 256), Mppad = round_up((int64_t)B * m->NP, 128);
+    const int64_t Mpad = pad_rows(m, B), Mppad = pad_patch_rows(m, B);
     size_t off = 0;
     auto take = [&](size_t bytes) -> char* {
         char* p = base ? base + off : nullptr;
         off += (size_t)round_up((int64_t)bytes, 256);
         return p;
     };
+    w.base = base; w.max_batch = base ? B : 0; w.train = train;
     w.Mpad = Mpad; w.Mppad = Mppad;
     // ---- common to both precisions: statistics, head, attack staging; the residual stream and its gradient stream are
     // fp32 in the fp32 parity mode and h16 on the 16-bit path (round 4: a LayerNorm pass moves 8 B per element, not 12 / 16) ----
@@ -598,7 +613,7 @@ static size_t carve(vl_model* m, int B, int train, char* base) {
     w.grad_img = (float*)take(img);
     w.stage_x0 = (float*)take(img); w.stage_adv = (float*)take(img);
     w.stage_labels = (int64_t*)take((size_t)B * 8);
-    if (m->f32) return f32_carve(m, B, train, base, off);
+    if (m->f32) return w.bytes = f32_carve(m, w, train, base, off);
     // ---- 16-bit operand path ----
     w.patches = (h16*)take((size_t)Mppad * m->PK * 2);
     w.h1.resize(L); w.h2.resize(L); w.a.resize(L); w.qkv.resize(L); w.ctx.resize(L); w.z.resize(L);
@@ -641,7 +656,11 @@ static size_t carve(vl_model* m, int B, int train, char* base) {
     // per-chunk copies of the LoRA gradient (deterministic weight gradients: lora_grad.hip); the LoRA parameters are the
     // first cls_w_off elements of the flat buffer
     w.wg_slab = train && m->cls_w_off > 0 ? (float*)take((size_t)lora_wgrad_chunks((int)((int64_t)B * m->T)) * (size_t)m->cls_w_off * 4) : nullptr;
-    return off;
+    return w.bytes = off;
+}
+static size_t carve_bytes(const vl_model* m, int B, int train) {
+    Workspace scratch;
+    return carve(m, scratch, B, train, nullptr);
 }
 
 static void drop_graphs(vl_model* m) {
@@ -656,20 +675,11 @@ static int chain_resources(vl_model* m) {
     return VL_OK;
 }
 
-// Two-chain PGD (model.h): each chain's activations for up to `cb` images, carved behind the main workspace.  carve() fills
-// m->ws, so the chain structs are swapped in while it runs.
+// Two-chain PGD (model.h): each half pass's activations for up to chain_images() images, carved behind the main workspace.
 static int chain_images(const vl_model* m, int max_batch) {
     if (m->f32 || m->pgd_chains == 1 || max_batch < 2) return 0;
     const int top = max_batch < vl_model::CHAIN_MAX_BATCH ? max_batch : vl_model::CHAIN_MAX_BATCH;
     return (top + 1) / 2;
-}
-static size_t chain_bytes(vl_model* m, int max_batch) {
-    const int cb = chain_images(m, max_batch);
-    if (!cb) return 0;
-    std::swap(m->ws, m->chain_ws[0]);
-    const size_t one = carve(m, cb, 0, nullptr);
-    std::swap(m->ws, m->chain_ws[0]);
-    return 2 * one;
 }
 
 int vl_plan(vl_model* m, int max_batch, int train, size_t* bytes) {
@@ -677,15 +687,16 @@ int vl_plan(vl_model* m, int max_batch, int train, size_t* bytes) {
     if (!m->f32) {
         // the 16-bit GEMM / attention kernels address an operand with 32-bit byte offsets from its base: the widest activation
         // ([token rows, max(3 D, MLP, 3 P^2)] h16) must stay below 4 GiB (ViT-B: 3 547 images per call, ViT-L: 2 660)
-        const int64_t rows = round_up((int64_t)max_batch * m->T, 256);
+        const int64_t rows = pad_rows(m, max_batch);
         const int64_t wide = std::max<int64_t>(std::max<int64_t>(3 * m->D, m->MLP), m->PK);
         if (rows * wide >= ((int64_t)1 << 31))
             return fail(VL_ERR_UNSUPPORTED, "max_batch %d: an activation of %lld x %lld 16-bit elements exceeds the 4 GiB the kernels' 32-bit "
                         "operand offsets reach; split the batch (at most %lld images per call for this architecture)", max_batch,
                         (long long)rows, (long long)wide, (long long)((((int64_t)1 << 31) / wide - 255) / m->T));
     }
-    *bytes = carve(m, max_batch, train, nullptr) + chain_bytes(m, max_batch);
-    m->ws.max_batch = 0;   // a plan alone does not arm the workspace
+    const int cb = chain_images(m, max_batch);
+    *bytes = carve_bytes(m, max_batch, train) + (cb ? 2 * carve_bytes(m, cb, 0) : 0);
+    m->main.ws.max_batch = 0;   // a plan alone does not arm the workspace (and disarms a live one; its pointers stay as they are)
     m->plan_batch = max_batch; m->plan_train = train;
     return VL_OK;
 }
@@ -696,42 +707,35 @@ int vl_set_workspace(vl_model* m, void* wsp, size_t bytes) {
     if (m->plan_batch <= 0) return fail(VL_ERR_STATE, "vl_set_workspace before vl_plan");
     const int max_batch = m->plan_batch, train = m->plan_train;
     if (((uintptr_t)wsp) & 255) return fail(VL_ERR_ARG, "workspace must be 256-byte aligned");
-    const size_t main_need = carve(m, max_batch, train, nullptr);
-    const size_t need = main_need + chain_bytes(m, max_batch);
+    const int cb = chain_images(m, max_batch);
+    const size_t main_need = carve_bytes(m, max_batch, train), one = cb ? carve_bytes(m, cb, 0) : 0, need = main_need + 2 * one;
     if (bytes < need) return fail(VL_ERR_ARG, "workspace too small: %zu < %zu", bytes, need);
-    carve(m, max_batch, train, (char*)wsp);
-    m->ws.base = (char*)wsp; m->ws.bytes = bytes; m->ws.max_batch = max_batch; m->ws.train = train;
-    m->chain_batch = chain_images(m, max_batch);
-    for (int c = 0; c < 2 && m->chain_batch; ++c) {
-        char* cbase = (char*)wsp + main_need + (size_t)c * ((need - main_need) / 2);
-        std::swap(m->ws, m->chain_ws[c]);
-        carve(m, m->chain_batch, 0, cbase);
-        m->ws.base = cbase; m->ws.bytes = (need - main_need) / 2; m->ws.max_batch = m->chain_batch; m->ws.train = 0;
-        std::swap(m->ws, m->chain_ws[c]);
-    }
+    carve(m, m->main.ws, max_batch, train, (char*)wsp);
+    m->chain_batch = cb;
+    for (int c = 0; c < 2 && cb; ++c) carve(m, m->half[c].ws, cb, 0, (char*)wsp + main_need + (size_t)c * one);
     if (hipMemset(wsp, 0, need) != hipSuccess) return fail(VL_ERR_HIP, "hipMemset(workspace) failed");
     drop_graphs(m);
-    m->cur_B = 0;
+    m->main.B = m->main.have_loss = 0;      // a new workspace holds no forward
     return VL_OK;
 }
 
 // ---- forward ---------------------------------------------------------------------------------
-static int forward_impl(vl_model* m, const float* x, int B, int normalise, int train, hipStream_t s) {
-    Workspace& w = m->ws;
+// one forward of B images in pass `p`; on success p holds it (B, rows, norm, train, cls_only) and no loss yet
+static int forward_impl(vl_model* m, Pass& p, const float* x, int B, int normalise, int train, hipStream_t s) {
+    Workspace& w = p.ws;
     if (B <= 0 || B > w.max_batch) return fail(VL_ERR_STATE, "batch %d exceeds planned workspace (%d)", B, w.max_batch);
     if (train && !w.train) return fail(VL_ERR_STATE, "workspace was not planned for training");
     if (train && m->cfg.lora_merged) return fail(VL_ERR_STATE, "training needs lora_merged = 0");
     if (train && m->r && m->cfg.lora_dropout >= 1.f) return fail(VL_ERR_ARG, "lora_dropout must be < 1");
     const int D = m->D, L = m->L, T = m->T;
-    const int Mpad = (int)round_up((int64_t)B * T, m->f32 ? 128 : 256), Mppad = (int)round_up((int64_t)B * m->NP, 128);
+    const int Mpad = (int)pad_rows(m, B), Mppad = (int)pad_patch_rows(m, B);
     const int M = B * T;
-    m->cur_M = M;
-    m->cur_train = train;
+    p.rows = M; p.train = train; p.cls_only = 0;
     if (train) m->drop_seed = m->drop_base + (++m->drop_calls);
     if (m->f32) {
-        int rc = f32_forward(m, x, B, normalise, train, s);
+        int rc = f32_forward(m, p, x, B, normalise, s);
         if (rc) return rc;
-        m->cur_B = B; m->cur_norm = normalise; m->cur_train = train; m->have_loss = 0;
+        p.B = B; p.norm = normalise; p.have_loss = 0;
         return VL_OK;
     }
     k_patch_gather(x, w.patches, B, m->S, m->P, normalise, m->mean, m->stdv, s);
@@ -749,70 +753,67 @@ static int forward_impl(vl_model* m, const float* x, int B, int normalise, int t
     const bool re = m->resid_epi >= 1, re2 = m->resid_epi >= 2;      // o projection / fc2
     // eval-mode forwards only feed logits and input gradients: the last layer runs on the CLS rows alone
     const bool cls_only = m->dead_rows && !train;
-    m->cur_cls_only = 0;
     for (int l = 0; l < L; ++l) {
         Layer& ly = m->layers[l];
         GemmArgs g;
-        const int n1 = fused_down_fwd(m, ly.lin[LQKV]);      // t of the qkv projection comes out of LN1
+        const int n1 = fused_down_fwd(m, p, ly.lin[LQKV]);      // t of the qkv projection comes out of LN1
         const h16* P1 = n1 ? ly.lin[LQKV].Ad : nullptr;
         if (l == 0 || re2) k_layernorm_fwd16(w.xs16[2 * l], w.h1[l], w.mean[2 * l], w.rstd[2 * l], ly.ln1_g, ly.ln1_b, M, D, m->cfg.ln_eps, nullptr, nullptr, P1, n1, w.t[LQKV][l], s, ef);
         else k_layernorm_fwd16(w.xs16[2 * l - 1], w.h1[l], w.mean[2 * l], w.rstd[2 * l], ly.ln1_g, ly.ln1_b, M, D, m->cfg.ln_eps, delta, w.xs16[2 * l], P1, n1, w.t[LQKV][l], s, ef);
         memset(&g, 0, sizeof g); g.C = w.qkv[l]; g.ldc = 3 * D;
-        linear_fwd(m, ly.lin[LQKV], w.h1[l], w.t[LQKV][l], Mpad, g, EPI_STORE_H16, s, l * 4 + LQKV, n1 > 0);
+        linear_fwd(m, p, ly.lin[LQKV], w.h1[l], w.t[LQKV][l], Mpad, M, g, EPI_STORE_H16, s, l * 4 + LQKV, n1 > 0);
         if (cls_only && l == L - 1) {
             // ---- last layer, CLS rows only (cls_path.hip): B rows from here to the classifier ----
             Workspace::Cls& c = w.c;
             const int Bc = (int)c.Bc;
             if (k_attn_cls_fwd(w.qkv[l], c.ctx, c.lse, B, T, m->H, D, s)) return fail(VL_ERR_UNSUPPORTED, "attention: T > 256");
-            m->cur_M = B;                                          // rows the compact GEMMs may store
             memset(&g, 0, sizeof g); g.C = c.delta; g.ldc = D;
-            linear_fwd(m, ly.lin[LO], c.ctx, c.t, Bc, g, EPI_STORE_H16, s, l * 4 + LO);
+            linear_fwd(m, p, ly.lin[LO], c.ctx, c.t, Bc, B, g, EPI_STORE_H16, s, l * 4 + LO);
             k_gather_rows(w.xs16[2 * l], c.x0, B, D, (int64_t)T * D, s);
-            const int n2c = fused_down_fwd(m, ly.lin[LFC1]);
+            const int n2c = fused_down_fwd(m, p, ly.lin[LFC1]);
             k_layernorm_fwd(c.x0, c.h2, c.mean, c.rstd, ly.ln2_g, ly.ln2_b, B, D, m->cfg.ln_eps, c.delta, c.x1,
                             n2c ? ly.lin[LFC1].Ad : nullptr, n2c, c.t, s);
             memset(&g, 0, sizeof g); g.C = c.a; g.ldc = m->MLP; g.C2 = c.z; g.ldc2 = m->MLP;
-            linear_fwd(m, ly.lin[LFC1], c.h2, c.t, Bc, g, EPI_GELU, s, l * 4 + LFC1, n2c > 0);
+            linear_fwd(m, p, ly.lin[LFC1], c.h2, c.t, Bc, B, g, EPI_GELU, s, l * 4 + LFC1, n2c > 0);
             memset(&g, 0, sizeof g); g.C = c.delta; g.ldc = D;
-            linear_fwd(m, ly.lin[LFC2], c.a, c.t, Bc, g, EPI_STORE_H16, s, l * 4 + LFC2);
+            linear_fwd(m, p, ly.lin[LFC2], c.a, c.t, Bc, B, g, EPI_STORE_H16, s, l * 4 + LFC2);
             k_layernorm_fwd(c.x1, nullptr, nullptr, nullptr, nullptr, nullptr, B, D, m->cfg.ln_eps, c.delta, c.x2, nullptr, 0, nullptr, s);
-            m->cur_M = M;
             k_head_fwd(c.x2, B, 1, D, m->C, m->cfg.ln_eps, m->lnf_g, m->lnf_b, m->flat + m->cls_w_off,
                        m->flat + m->cls_b_off, w.xhat, w.xf, w.rstd_f, w.logits, s);
-            m->cur_B = B; m->cur_norm = normalise; m->cur_train = train; m->have_loss = 0; m->cur_cls_only = 1;
+            p.B = B; p.norm = normalise; p.have_loss = 0; p.cls_only = 1;
             return VL_OK;
         }
         // large batches: one persistent workgroup per image walks the heads; the LoRA down projection of the output
         // projection (t = ctx Ad^T) is summed over heads inside it, the skinny GEMM over ctx disappears
         const bool img = attn_img(m, B);
-        const bool t_o = img && down_fusable(m, ly.lin[LO]) && !vl_drop_on(m);
+        const bool t_o = img && down_fusable(m, ly.lin[LO]) && !vl_drop_on(m, p);
         if (img) {
             if (k_attention_img_fwd(w.qkv[l], w.ctx[l], w.lse[l], B, T, m->H, D, t_o ? ly.lin[LO].Ad : nullptr, w.t[LO][l], m->r, s))
                 return fail(VL_ERR_UNSUPPORTED, "attention: T > 224");
         } else if (k_attention32_fwd(w.qkv[l], w.ctx[l], w.lse[l], B, T, m->H, D, s)) return fail(VL_ERR_UNSUPPORTED, "attention: T > 224");
         memset(&g, 0, sizeof g); g.C = delta; g.ldc = D;
         if (re) { g.C = w.xs16[2 * l + 1]; g.R = w.xs16[2 * l]; g.ldr = D; }
-        linear_fwd(m, ly.lin[LO], w.ctx[l], w.t[LO][l], Mpad, g, re ? EPI_RESID_H16 : EPI_STORE_H16, s, l * 4 + LO, t_o);
-        const int n2 = fused_down_fwd(m, ly.lin[LFC1]);      // t of fc1 (r columns) comes out of LN2
+        linear_fwd(m, p, ly.lin[LO], w.ctx[l], w.t[LO][l], Mpad, M, g, re ? EPI_RESID_H16 : EPI_STORE_H16, s, l * 4 + LO, t_o);
+        const int n2 = fused_down_fwd(m, p, ly.lin[LFC1]);      // t of fc1 (r columns) comes out of LN2
         const h16* P2 = n2 ? ly.lin[LFC1].Ad : nullptr;
         if (re) k_layernorm_fwd16(w.xs16[2 * l + 1], w.h2[l], w.mean[2 * l + 1], w.rstd[2 * l + 1], ly.ln2_g, ly.ln2_b, M, D, m->cfg.ln_eps, nullptr, nullptr, P2, n2, w.t[LFC1][l], s, ef);
         else k_layernorm_fwd16(w.xs16[2 * l], w.h2[l], w.mean[2 * l + 1], w.rstd[2 * l + 1], ly.ln2_g, ly.ln2_b, M, D, m->cfg.ln_eps, delta, w.xs16[2 * l + 1], P2, n2, w.t[LFC1][l], s, ef);
         memset(&g, 0, sizeof g); g.C = w.a[l]; g.ldc = m->MLP; g.C2 = w.z[l]; g.ldc2 = m->MLP;
-        linear_fwd(m, ly.lin[LFC1], w.h2[l], w.t[LFC1][l], Mpad, g, EPI_GELU, s, l * 4 + LFC1, n2 > 0);
+        linear_fwd(m, p, ly.lin[LFC1], w.h2[l], w.t[LFC1][l], Mpad, M, g, EPI_GELU, s, l * 4 + LFC1, n2 > 0);
         memset(&g, 0, sizeof g); g.C = delta; g.ldc = D;
         if (re2) { g.C = w.xs16[2 * l + 2]; g.R = w.xs16[2 * l + 1]; g.ldr = D; }
-        linear_fwd(m, ly.lin[LFC2], w.a[l], w.t[LFC2][l], Mpad, g, re2 ? EPI_RESID_H16 : EPI_STORE_H16, s, l * 4 + LFC2);
+        linear_fwd(m, p, ly.lin[LFC2], w.a[l], w.t[LFC2][l], Mpad, M, g, re2 ? EPI_RESID_H16 : EPI_STORE_H16, s, l * 4 + LFC2);
     }
     if (!re2) k_layernorm_fwd16(w.xs16[2 * L - 1], nullptr, nullptr, nullptr, nullptr, nullptr, M, D, m->cfg.ln_eps, delta, w.xs16[2 * L], nullptr, 0, nullptr, s, ef);
     k_head_fwd16(w.xs16[2 * L], B, T, D, m->C, m->cfg.ln_eps, m->lnf_g, m->lnf_b, m->flat + m->cls_w_off,
                m->flat + m->cls_b_off, w.xhat, w.xf, w.rstd_f, w.logits, s);
-    m->cur_B = B; m->cur_norm = normalise; m->cur_train = train; m->have_loss = 0;
+    p.B = B; p.norm = normalise; p.have_loss = 0;
     return VL_OK;
 }
 
 int vl_forward(vl_model* m, const float* x, int batch, int normalise, int train, float* logits_out, void* stream) {
     if (!m || !x) return fail(VL_ERR_ARG, "null argument");
-    if (!m->ws.max_batch) return fail(VL_ERR_STATE, "no workspace: call vl_plan + vl_set_workspace first");
+    if (!m->main.ws.max_batch) return fail(VL_ERR_STATE, "no workspace: call vl_plan + vl_set_workspace first");
     hipStream_t s = (hipStream_t)stream;
     int rc = check_async(m);
     if (rc) return rc;
@@ -820,47 +821,38 @@ int vl_forward(vl_model* m, const float* x, int batch, int normalise, int train,
     m->fwd_chains = 0;
     const int b0 = (batch + 1) / 2, b1 = batch - b0;
     if (m->api_chains && !train && !m->f32 && m->chain_batch > 0 && batch >= 2 && b0 <= m->chain_batch &&
-        batch <= vl_model::CHAIN_MAX_BATCH && batch <= m->ws.max_batch && !capturing(s) && !g_prof) {
-        // two half-batch chains (model.h): chain 0 on the caller's stream, chain 1 on the side stream, logits gathered in the main workspace
+        batch <= vl_model::CHAIN_MAX_BATCH && batch <= m->main.ws.max_batch && !capturing(s) && !g_prof) {
+        // two half-batch chains (model.h): each half pass runs its own forward, the logits are gathered in the main pass
         if ((rc = chain_resources(m))) return rc;
-        float* const main_logits = m->ws.logits;
         const int64_t img = (int64_t)3 * m->S * m->S;
-        HIPCHK(hipEventRecord(m->ev_fork, s));
-        HIPCHK(hipStreamWaitEvent(m->side_stream, m->ev_fork, 0));
-        int rcs[2];
-        for (int c = 0; c < 2; ++c) {
-            hipStream_t sc = c ? m->side_stream : s;
-            const int bc = c ? b1 : b0;
-            std::swap(m->ws, m->chain_ws[c]);
-            rcs[c] = forward_impl(m, x + (c ? b0 * img : 0), bc, normalise, 0, sc);
-            float* const cl = m->ws.logits;
-            std::swap(m->ws, m->chain_ws[c]);
-            m->chain_B[c] = bc; m->chain_cls[c] = m->cur_cls_only;
-            if (!rcs[c]) (void)hipMemcpyAsync(main_logits + (size_t)(c ? b0 : 0) * m->C, cl, (size_t)bc * m->C * sizeof(float), hipMemcpyDeviceToDevice, sc);
-        }
-        HIPCHK(hipEventRecord(m->ev_join, m->side_stream));
-        HIPCHK(hipStreamWaitEvent(s, m->ev_join, 0));
-        if (rcs[0] || rcs[1]) { m->cur_B = 0; return rcs[0] ? rcs[0] : rcs[1]; }
-        m->cur_B = batch; m->cur_M = batch * m->T; m->cur_norm = normalise; m->cur_train = 0; m->have_loss = 0; m->fwd_chains = 2;
+        rc = on_both_halves(m, s, [&](int c, Pass& h, hipStream_t sc) {
+            const int bc = c ? b1 : b0, rcc = forward_impl(m, h, x + (c ? b0 * img : 0), bc, normalise, 0, sc);
+            if (!rcc) (void)hipMemcpyAsync(m->main.ws.logits + (size_t)(c ? b0 : 0) * m->C, h.ws.logits, (size_t)bc * m->C * sizeof(float), hipMemcpyDeviceToDevice, sc);
+            return rcc;
+        });
+        Pass& p = m->main;          // holds the whole batch's logits; the activations stay in the half passes
+        if (rc) { p.B = 0; return rc; }
+        p.B = batch; p.rows = batch * m->T; p.norm = normalise; p.train = 0; p.have_loss = 0; m->fwd_chains = 2;
     } else {
-        rc = forward_impl(m, x, batch, normalise, train, s);
+        rc = forward_impl(m, m->main, x, batch, normalise, train, s);
         if (rc) return rc;
     }
     if (logits_out)
-        HIPCHK(hipMemcpyAsync(logits_out, m->ws.logits, (size_t)batch * m->C * sizeof(float), hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(logits_out, m->main.ws.logits, (size_t)batch * m->C * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (!capturing(s)) return check_launch("vl_forward");
     return VL_OK;
 }
 
 int vl_loss_ce(vl_model* m, const int64_t* labels, float* loss_out, void* stream) {
     if (!m || !labels) return fail(VL_ERR_ARG, "null argument");
-    if (!m->cur_B) return fail(VL_ERR_STATE, "vl_loss_ce before vl_forward");
+    Pass& p = m->main;
+    if (!p.B) return fail(VL_ERR_STATE, "vl_loss_ce before vl_forward");
     hipStream_t s = (hipStream_t)stream;
     int rc = check_async(m);
     if (rc) return rc;
-    k_ce_loss(m->ws.logits, labels, m->cur_B, m->C, m->ws.dlogits, m->ws.loss_img, m->ws.loss, m->err_flag, s);
-    if (loss_out) HIPCHK(hipMemcpyAsync(loss_out, m->ws.loss, sizeof(float), hipMemcpyDeviceToDevice, s));
-    m->have_loss = 1;
+    k_ce_loss(p.ws.logits, labels, p.B, m->C, p.ws.dlogits, p.ws.loss_img, p.ws.loss, m->err_flag, s);
+    if (loss_out) HIPCHK(hipMemcpyAsync(loss_out, p.ws.loss, sizeof(float), hipMemcpyDeviceToDevice, s));
+    p.have_loss = 1;
     return VL_OK;
 }
 
@@ -870,15 +862,15 @@ int vl_loss_ce(vl_model* m, const int64_t* labels, float* loss_out, void* stream
 // K10 fused into the patch-gradient epilogue: the pixel gradient never goes to HBM (vl_pgd_attack; vl_pgd_step stays the ABI entry)
 struct PgdFuse { float* adv; const float* x0; float eps, alpha; };
 
-static int backward_impl(vl_model* m, float* grad_x, float* flat_grad, hipStream_t s, const PgdFuse* pf = nullptr) {
-    Workspace& w = m->ws;
-    if (!m->have_loss) return fail(VL_ERR_STATE, "backward before vl_loss_ce");
-    const int B = m->cur_B, D = m->D, L = m->L, T = m->T, MLP = m->MLP, r = m->r;
-    const int Mpad = (int)round_up((int64_t)B * T, m->f32 ? 128 : 256), Mppad = (int)round_up((int64_t)B * m->NP, 128);
+static int backward_impl(vl_model* m, Pass& p, float* grad_x, float* flat_grad, hipStream_t s, const PgdFuse* pf = nullptr) {
+    Workspace& w = p.ws;
+    if (!p.have_loss) return fail(VL_ERR_STATE, "backward before vl_loss_ce");
+    const int B = p.B, D = m->D, L = m->L, T = m->T, MLP = m->MLP, r = m->r;
+    const int Mpad = (int)pad_rows(m, B), Mppad = (int)pad_patch_rows(m, B);
     const int M = B * T;
     const float sc = m->scaling;
-    if (flat_grad && !m->cur_train) return fail(VL_ERR_STATE, "vl_backward_lora needs vl_forward(train=1)");
-    if (m->f32) return f32_backward(m, grad_x, flat_grad, s);
+    if (flat_grad && !p.train) return fail(VL_ERR_STATE, "vl_backward_lora needs vl_forward(train=1)");
+    if (m->f32) return f32_backward(m, p, grad_x, flat_grad, s);
     // fp16 gradients: every image's dLoss/dlogits row is scaled by a power of two S_b so that its largest entry lands
     // in [2^9, 2^10) -- the backward chain is linear and per image, so results are exact up to under/overflow and
     // the input gradient of a confidently classified image (dlogits ~ 1e-6) keeps its precision.  With parameter
@@ -889,7 +881,7 @@ static int backward_impl(vl_model* m, float* grad_x, float* flat_grad, hipStream
         // adapter have no elements in the flat buffer)
         k_classifier_grad(w.dlogits, w.xf, B, D, m->C, flat_grad + m->cls_w_off, flat_grad + m->cls_b_off, s);
     }
-    const bool cls_only = m->cur_cls_only != 0;
+    const bool cls_only = p.cls_only != 0;
     if (cls_only && flat_grad) return fail(VL_ERR_STATE, "parameter gradients need a train-mode forward");
     if (!cls_only) {
         // the residual-gradient stream (h16, updated in place by every LayerNorm backward; also the A operand of the dgrad GEMMs)
@@ -900,7 +892,7 @@ static int backward_impl(vl_model* m, float* grad_x, float* flat_grad, hipStream
     // LoRA weight gradients of one projection: dy [M,out], x [M,in], t/u [M,kext]
     auto wgrad = [&](const Linear& ln, const h16* dy, const h16* x, const h16* t, const h16* u, uint32_t stream_id) {
         if (!flat_grad || ln.slots.empty()) return;
-        if (vl_drop_on(m)) {       // dA sees the dropped branch input: regenerate it (same seed / stream as the forward)
+        if (vl_drop_on(m, p)) {       // dA sees the dropped branch input: regenerate it (same seed / stream as the forward)
             k_dropout(x, w.xd, (int64_t)M * ln.in, m->drop_seed, stream_id, m->cfg.lora_dropout, s);
             x = w.xd;
         }
@@ -920,20 +912,18 @@ static int backward_impl(vl_model* m, float* grad_x, float* flat_grad, hipStream
             // ---- last layer: the gradient lives on the CLS rows until dK / dV of the attention spread it over every token ----
             Workspace::Cls& c = w.c;
             const int Bc = (int)c.Bc;
-            m->cur_M = B;
             k_head_bwd(w.dlogits, w.gscale, m->flat + m->cls_w_off, m->lnf_g, w.xhat, w.rstd_f, B, 1, D, m->C, c.dres[0], c.dres_h, s);
             memset(&g, 0, sizeof g); g.C = c.dz; g.ldc = MLP; g.R = c.z; g.ldr = MLP;
-            linear_dgrad(m, ly.lin[LFC2], c.dres_h, c.u, Bc, g, EPI_GELU_BWD, s, l * 4 + LFC2);
+            linear_dgrad(m, p, ly.lin[LFC2], c.dres_h, c.u, Bc, B, g, EPI_GELU_BWD, s, l * 4 + LFC2);
             memset(&g, 0, sizeof g); g.C = c.dh; g.ldc = D;
-            linear_dgrad(m, ly.lin[LFC1], c.dz, c.u, Bc, g, EPI_STORE_H16, s, l * 4 + LFC1);
+            linear_dgrad(m, p, ly.lin[LFC1], c.dz, c.u, Bc, B, g, EPI_STORE_H16, s, l * 4 + LFC1);
             const int foc = fused_down(m, ly.lin[LO]);
             k_layernorm_bwd(c.dh, c.x1, c.mean, c.rstd, ly.ln2_g, c.dres[0], c.dres[1], c.dres_h, B, D, ly.lin[LO].Bd, foc, c.u, s, m->err_flag);
             memset(&g, 0, sizeof g); g.C = c.dctx; g.ldc = D;
-            linear_dgrad(m, ly.lin[LO], c.dres_h, c.u, Bc, g, EPI_STORE_H16, s, l * 4 + LO, foc > 0);
-            m->cur_M = M;
+            linear_dgrad(m, p, ly.lin[LO], c.dres_h, c.u, Bc, B, g, EPI_STORE_H16, s, l * 4 + LO, foc > 0);
             if (k_attn_cls_bwd(w.qkv[l], c.ctx, c.dctx, c.lse, w.dqkv, B, T, m->H, D, s)) return fail(VL_ERR_UNSUPPORTED, "attention: T > 256");
             memset(&g, 0, sizeof g); g.C = w.dh; g.ldc = D;
-            linear_dgrad(m, ly.lin[LQKV], w.dqkv, w.u, Mpad, g, EPI_STORE_H16, s, l * 4 + LQKV);
+            linear_dgrad(m, p, ly.lin[LQKV], w.dqkv, w.u, Mpad, M, g, EPI_STORE_H16, s, l * 4 + LQKV);
             // residual gradient entering LN1: zero except the CLS rows
             k_zero(w.dres_h, (size_t)Mpad * D * sizeof(h16), s);
             k_scatter_rows(c.dres[1], w.dres_h, B, D, (int64_t)T * D, s);
@@ -945,17 +935,17 @@ static int backward_impl(vl_model* m, float* grad_x, float* flat_grad, hipStream
         // MLP: dz = (dx2 Wfc2 (+LoRA)) * gelu'(z)
         memset(&g, 0, sizeof g); g.C = w.dz; g.ldc = MLP; g.R = w.z[l]; g.ldr = MLP;
         // u of this dgrad came with dres_h from the LayerNorm backward of the layer above (not for the top layer)
-        linear_dgrad(m, ly.lin[LFC2], w.dres_h, w.u, Mpad, g, EPI_GELU_BWD, s, l * 4 + LFC2, l < L - 1 && fused_down(m, ly.lin[LFC2]) > 0);
+        linear_dgrad(m, p, ly.lin[LFC2], w.dres_h, w.u, Mpad, M, g, EPI_GELU_BWD, s, l * 4 + LFC2, l < L - 1 && fused_down(m, ly.lin[LFC2]) > 0);
         wgrad(ly.lin[LFC2], w.dres_h, w.a[l], w.t[LFC2][l], w.u, l * 4 + LFC2);
         memset(&g, 0, sizeof g); g.C = w.dh; g.ldc = D;
-        linear_dgrad(m, ly.lin[LFC1], w.dz, w.u, Mpad, g, EPI_STORE_H16, s, l * 4 + LFC1);
+        linear_dgrad(m, p, ly.lin[LFC1], w.dz, w.u, Mpad, M, g, EPI_STORE_H16, s, l * 4 + LFC1);
         wgrad(ly.lin[LFC1], w.dz, w.h2[l], w.t[LFC1][l], w.u, l * 4 + LFC1);
         const int fo = fused_down(m, ly.lin[LO]);
         k_layernorm_bwd16(w.dh, w.xs16[2 * l + 1], w.mean[2 * l + 1], w.rstd[2 * l + 1], ly.ln2_g, w.dres_h, M, D, ly.lin[LO].Bd, fo, w.u, s,
                           m->err_flag);
         // attention block
         memset(&g, 0, sizeof g); g.C = w.dctx; g.ldc = D;
-        linear_dgrad(m, ly.lin[LO], w.dres_h, w.u, Mpad, g, EPI_STORE_H16, s, l * 4 + LO, fo > 0);
+        linear_dgrad(m, p, ly.lin[LO], w.dres_h, w.u, Mpad, M, g, EPI_STORE_H16, s, l * 4 + LO, fo > 0);
         wgrad(ly.lin[LO], w.dres_h, w.ctx[l], w.t[LO][l], w.u, l * 4 + LO);
         const bool img = attn_img(m, B);
         const bool u_qkv = img && down_fusable(m, ly.lin[LQKV]);
@@ -968,7 +958,7 @@ static int backward_impl(vl_model* m, float* grad_x, float* flat_grad, hipStream
         } else if (k_attention32_bwd(w.qkv[l], w.ctx[l], w.dctx, w.lse[l], w.dqkv, B, T, m->H, D, s))
             return fail(VL_ERR_UNSUPPORTED, "attention: T > 224");
         memset(&g, 0, sizeof g); g.C = w.dh; g.ldc = D;
-        linear_dgrad(m, ly.lin[LQKV], w.dqkv, w.u, Mpad, g, EPI_STORE_H16, s, l * 4 + LQKV, u_qkv);
+        linear_dgrad(m, p, ly.lin[LQKV], w.dqkv, w.u, Mpad, M, g, EPI_STORE_H16, s, l * 4 + LQKV, u_qkv);
         wgrad(ly.lin[LQKV], w.dqkv, w.h1[l], w.t[LQKV][l], w.u, l * 4 + LQKV);
         const int ff = l > 0 ? fused_down(m, m->layers[l - 1].lin[LFC2]) : 0;     // next consumer: fc2 dgrad of the layer below
         k_layernorm_bwd16(w.dh, w.xs16[2 * l], w.mean[2 * l], w.rstd[2 * l], ly.ln1_g, w.dres_h, M, D,
@@ -981,7 +971,7 @@ static int backward_impl(vl_model* m, float* grad_x, float* flat_grad, hipStream
         GemmArgs g = gemm_args(w.dres_h, D, m->WpeT, D, D, Mppad, m->PK);
         g.Mvalid = B * m->NP; g.C = grad_x; g.a_gather = 1;
         g.tokens = T; g.patches = m->NP; g.grid = m->G; g.psize = m->P; g.img = m->S;
-        for (int c = 0; c < 3; ++c) g.inv_std[c] = m->cur_norm ? 1.f / m->stdv[c] : 1.f;
+        for (int c = 0; c < 3; ++c) g.inv_std[c] = p.norm ? 1.f / m->stdv[c] : 1.f;
         g.row_scale = w.inv_gscale;          // per image: undoes the gradient scale
         g.err_flag = m->err_flag;
         if (pf) {                            // sign -> alpha step -> eps projection -> clamp on the gradient in registers
@@ -1002,10 +992,10 @@ int vl_check_errors(vl_model* m, void* stream) {
 
 int vl_set_dlogits(vl_model* m, const float* dlogits, void* stream) {
     if (!m || !dlogits) return fail(VL_ERR_ARG, "null argument");
-    if (!m->cur_B) return fail(VL_ERR_STATE, "vl_set_dlogits before vl_forward");
-    HIPCHK(hipMemcpyAsync(m->ws.dlogits, dlogits, (size_t)m->cur_B * m->C * sizeof(float), hipMemcpyDeviceToDevice,
+    if (!m->main.B) return fail(VL_ERR_STATE, "vl_set_dlogits before vl_forward");
+    HIPCHK(hipMemcpyAsync(m->main.ws.dlogits, dlogits, (size_t)m->main.B * m->C * sizeof(float), hipMemcpyDeviceToDevice,
                           (hipStream_t)stream));
-    m->have_loss = 1;
+    m->main.have_loss = 1;
     return VL_OK;
 }
 
@@ -1015,32 +1005,21 @@ static int backward_api(vl_model* m, float* grad_x, float* flat_grad, hipStream_
     if (m->fwd_chains == 2) {
         // the forward ran as two chains: so does the backward, each from its slice of the whole batch's dLoss/dlogits
         if (flat_grad) return fail(VL_ERR_STATE, "vl_backward_lora needs vl_forward(train=1)");
-        if (!m->have_loss) return fail(VL_ERR_STATE, "backward before vl_loss_ce");
+        if (!m->main.have_loss) return fail(VL_ERR_STATE, "backward before vl_loss_ce");
         if ((rc = chain_resources(m))) return rc;
-        const int batch = m->cur_B, b0 = m->chain_B[0];
-        const float* const main_dlogits = m->ws.dlogits;
+        const int b0 = m->half[0].B;
         const int64_t img = (int64_t)3 * m->S * m->S;
-        HIPCHK(hipEventRecord(m->ev_fork, s));
-        HIPCHK(hipStreamWaitEvent(m->side_stream, m->ev_fork, 0));
-        int rcs[2];
-        for (int c = 0; c < 2; ++c) {
-            hipStream_t sc = c ? m->side_stream : s;
-            std::swap(m->ws, m->chain_ws[c]);
-            (void)hipMemcpyAsync(m->ws.dlogits, main_dlogits + (size_t)(c ? b0 : 0) * m->C, (size_t)m->chain_B[c] * m->C * sizeof(float),
+        rc = on_both_halves(m, s, [&](int c, Pass& h, hipStream_t sc) {
+            (void)hipMemcpyAsync(h.ws.dlogits, m->main.ws.dlogits + (size_t)(c ? b0 : 0) * m->C, (size_t)h.B * m->C * sizeof(float),
                                  hipMemcpyDeviceToDevice, sc);
-            m->cur_B = m->chain_B[c]; m->cur_cls_only = m->chain_cls[c]; m->have_loss = 1;
-            m->cur_M = m->chain_B[c] * m->T;          // Mvalid of this chain's dgrad GEMMs: its own rows (round-4 ADVICE: pad rows of the chain workspace were stored with dead_rows = 0)
-            rcs[c] = backward_impl(m, grad_x ? grad_x + (c ? b0 * img : 0) : nullptr, nullptr, sc);
-            std::swap(m->ws, m->chain_ws[c]);
-        }
-        m->cur_B = batch; m->cur_M = batch * m->T;
-        HIPCHK(hipEventRecord(m->ev_join, m->side_stream));
-        HIPCHK(hipStreamWaitEvent(s, m->ev_join, 0));
-        if (rcs[0] || rcs[1]) return rcs[0] ? rcs[0] : rcs[1];
+            h.have_loss = 1;
+            return backward_impl(m, h, grad_x ? grad_x + (c ? b0 * img : 0) : nullptr, nullptr, sc);
+        });
+        if (rc) return rc;
         if (!capturing(s)) return check_launch("vl_backward");
         return VL_OK;
     }
-    rc = backward_impl(m, grad_x, flat_grad, s);
+    rc = backward_impl(m, m->main, grad_x, flat_grad, s);
     if (rc) return rc;
     if (!capturing(s)) return check_launch("vl_backward");
     return VL_OK;
@@ -1080,8 +1059,8 @@ int vl_set_dropout_seed(vl_model* m, uint64_t seed) {
 // projection `proj` (0 = fused qkv, 1 = attention out, 2 = fc1, 3 = fc2) of `layer`: [B*T, in] fp32.
 int vl_dropout_mask(vl_model* m, int layer, int proj, float* out, void* stream) {
     if (!m || !out || layer < 0 || layer >= m->L || proj < 0 || proj > 3) return fail(VL_ERR_ARG, "bad argument");
-    if (!m->cur_train || !(m->cfg.lora_dropout > 0.f)) return fail(VL_ERR_STATE, "no train-mode forward with dropout");
-    k_dropout_mask(out, (int64_t)m->cur_M * m->layers[layer].lin[proj].in, m->drop_seed, (uint32_t)(layer * 4 + proj),
+    if (!m->main.train || !(m->cfg.lora_dropout > 0.f)) return fail(VL_ERR_STATE, "no train-mode forward with dropout");
+    k_dropout_mask(out, (int64_t)m->main.rows * m->layers[layer].lin[proj].in, m->drop_seed, (uint32_t)(layer * 4 + proj),
                    m->cfg.lora_dropout, (hipStream_t)stream);
     return VL_OK;
 }
@@ -1160,32 +1139,32 @@ static void dump_graph(hipGraph_t graph) {
     fclose(f);
 }
 
-static int pgd_iteration(vl_model* m, const float* x0, const int64_t* labels, int B, float eps, float alpha, float* adv,
+static int pgd_iteration(vl_model* m, Pass& p, const float* x0, const int64_t* labels, int B, float eps, float alpha, float* adv,
                          hipStream_t s) {
-    int rc = forward_impl(m, adv, B, 1, 0, s);
+    int rc = forward_impl(m, p, adv, B, 1, 0, s);
     if (rc) return rc;
-    k_ce_loss(m->ws.logits, labels, B, m->C, m->ws.dlogits, m->ws.loss_img, m->ws.loss, m->err_flag, s);
-    m->have_loss = 1;
+    k_ce_loss(p.ws.logits, labels, B, m->C, p.ws.dlogits, p.ws.loss_img, p.ws.loss, m->err_flag, s);
+    p.have_loss = 1;
     if (m->fuse_pgd && !m->f32) {
         const PgdFuse pf = {adv, x0, eps, alpha};
-        return backward_impl(m, nullptr, nullptr, s, &pf);
+        return backward_impl(m, p, nullptr, nullptr, s, &pf);
     }
-    rc = backward_impl(m, m->ws.grad_img, nullptr, s);
+    rc = backward_impl(m, p, p.ws.grad_img, nullptr, s);
     if (rc) return rc;
-    k_pgd_step(adv, x0, m->ws.grad_img, eps, alpha, 0.f, 1.f, (int64_t)B * 3 * m->S * m->S, s, m->err_flag);
+    k_pgd_step(adv, x0, p.ws.grad_img, eps, alpha, 0.f, 1.f, (int64_t)B * 3 * m->S * m->S, s, m->err_flag);
     return VL_OK;
 }
 
 int vl_pgd_attack(vl_model* m, const float* x0, const int64_t* labels, int batch, float eps, float alpha, int steps,
                   int random_start, uint64_t seed, float* adv_out, void* stream) {
     if (!m || !x0 || !labels || !adv_out) return fail(VL_ERR_ARG, "bad argument");
-    if (!m->ws.max_batch) return fail(VL_ERR_STATE, "no workspace");
-    if (batch <= 0 || batch > m->ws.max_batch) return fail(VL_ERR_STATE, "batch exceeds planned workspace");
+    if (!m->main.ws.max_batch) return fail(VL_ERR_STATE, "no workspace");
+    if (batch <= 0 || batch > m->main.ws.max_batch) return fail(VL_ERR_STATE, "batch exceeds planned workspace");
     hipStream_t s = (hipStream_t)stream;
     int rc = check_async(m);
     if (rc) return rc;
     if (m->dirty && (rc = vl_lora_commit(m, stream))) return rc;     // the attack sees the CURRENT adapters
-    Workspace& w = m->ws;
+    Workspace& w = m->main.ws;
     const int64_t n = (int64_t)batch * 3 * m->S * m->S;
     // Persistent staging: the captured iteration only ever reads / writes the workspace's x0 / labels / adv buffers,
     // so ONE executable graph per (batch, eps, alpha) serves every batch of a run whatever tensors the caller passes
@@ -1199,30 +1178,22 @@ int vl_pgd_attack(vl_model* m, const float* x0, const int64_t* labels, int batch
     const int b0 = (batch + 1) / 2, b1 = batch - b0;
     const bool chain_fits = m->chain_batch > 0 && batch >= 2 && b0 <= m->chain_batch;
     const int chains = (chain_fits && (m->pgd_chains == 2 || (m->pgd_chains == 0 && batch <= vl_model::CHAIN_MAX_BATCH))) ? 2 : 1;
-    // one PGD iteration of the whole batch, enqueued on s0 (chains == 2: second half on s1 between a fork and a join event)
-    auto iteration = [&](hipStream_t s0, hipStream_t s1) -> int {
-        if (chains == 1) return pgd_iteration(m, sx0, slab, batch, eps, alpha, sadv, s0);
-        const int64_t off = (int64_t)b0 * 3 * m->S * m->S;
-        HIPCHK(hipEventRecord(m->ev_fork, s0));
-        HIPCHK(hipStreamWaitEvent(s1, m->ev_fork, 0));
-        int rc0, rc1;
-        std::swap(m->ws, m->chain_ws[0]);            // chain 0's activations become "the" workspace while its kernels are enqueued
-        rc0 = pgd_iteration(m, sx0, slab, b0, eps, alpha, sadv, s0);
-        std::swap(m->ws, m->chain_ws[0]);
-        std::swap(m->ws, m->chain_ws[1]);
-        rc1 = pgd_iteration(m, sx0 + off, slab + b0, b1, eps, alpha, sadv + off, s1);
-        std::swap(m->ws, m->chain_ws[1]);
-        HIPCHK(hipEventRecord(m->ev_join, s1));
-        HIPCHK(hipStreamWaitEvent(s0, m->ev_join, 0));
-        m->cur_B = 0;                 // the handle holds no forward of the whole batch: a backward call needs its own forward
-        return rc0 ? rc0 : rc1;
+    // one PGD iteration of half pass c over its slice of the staged batch
+    const int64_t off1 = (int64_t)b0 * 3 * m->S * m->S;
+    auto half_iteration = [&](int c, Pass& h, hipStream_t sc) -> int {
+        return pgd_iteration(m, h, sx0 + (c ? off1 : 0), slab + (c ? b0 : 0), c ? b1 : b0, eps, alpha, sadv + (c ? off1 : 0), sc);
+    };
+    // one PGD iteration of the whole batch, enqueued on s (chains == 2: second half on the side stream between a fork and a join event)
+    auto iteration = [&]() -> int {
+        if (chains == 1) return pgd_iteration(m, m->main, sx0, slab, batch, eps, alpha, sadv, s);
+        return on_both_halves(m, s, half_iteration);
     };
     m->fwd_chains = 0;
     if (chains == 2 && (rc = chain_resources(m))) return rc;
     if (steps > 0) {
         if (!m->use_graph || g_prof || g_poison_lds) {
             for (int i = 0; i < steps; ++i)
-                if ((rc = iteration(s, m->side_stream))) return rc;
+                if ((rc = iteration())) return rc;
             if ((rc = check_launch("vl_pgd_attack"))) return rc;
         } else {
             hipGraphExec_t exec = nullptr, exec1 = nullptr;
@@ -1243,15 +1214,8 @@ int vl_pgd_attack(vl_model* m, const float* x0, const int64_t* labels, int batch
                     hipGraph_t graph = nullptr;
                     (void)hipGetLastError();
                     HIPCHK(hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeThreadLocal));
-                    int rcc;
-                    if (chains == 1) rcc = pgd_iteration(m, sx0, slab, batch, eps, alpha, sadv, m->cap_stream);
-                    else {
-                        const int64_t off = c ? (int64_t)b0 * 3 * m->S * m->S : 0;
-                        std::swap(m->ws, m->chain_ws[c]);
-                        rcc = pgd_iteration(m, sx0 + off, slab + (c ? b0 : 0), c ? b1 : b0, eps, alpha, sadv + off, m->cap_stream);
-                        std::swap(m->ws, m->chain_ws[c]);
-                        m->cur_B = 0;         // the handle holds no forward of the whole batch
-                    }
+                    const int rcc = chains == 1 ? pgd_iteration(m, m->main, sx0, slab, batch, eps, alpha, sadv, m->cap_stream)
+                                                : half_iteration(c, m->half[c], m->cap_stream);
                     hipError_t e = hipStreamEndCapture(m->cap_stream, &graph);
                     if (rcc) { if (graph) (void)hipGraphDestroy(graph); return rcc; }
                     if (e != hipSuccess) return fail(VL_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
@@ -1284,6 +1248,8 @@ int vl_pgd_attack(vl_model* m, const float* x0, const int64_t* labels, int batch
                 HIPCHK(hipStreamWaitEvent(s, m->ev_join, 0));
             }
         }
+        // two chains leave no forward of the whole batch in the main pass: a backward call needs its own forward and loss
+        if (chains == 2) m->main.B = m->main.have_loss = 0;
     }
     HIPCHK(hipMemcpyAsync(adv_out, w.stage_adv, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     return VL_OK;
@@ -1585,22 +1551,23 @@ int vl_debug_counter(vl_model* m, const char* what, int64_t* value) {
 int vl_debug_tensor(vl_model* m, const char* what, int layer, void** ptr, int64_t* numel, int* dtype) {
     // dtype: 0 = f32, 1 = fp16, 2 = bf16
     if (!m || !what || !ptr || !numel || !dtype) return fail(VL_ERR_ARG, "null argument");
-    Workspace& w = m->ws;
+    Workspace& w = m->main.ws;          // (after a two-chain forward the activations are in the half passes: not seen here)
     if (!w.max_batch) return fail(VL_ERR_STATE, "no workspace");
-    const int64_t MD = (int64_t)m->cur_B * m->T * m->D;
+    const int cur_B = m->main.B;
+    const int64_t MD = (int64_t)cur_B * m->T * m->D;
     {   // backward-side buffers (shared across layers: they hold what the LAST executed kernel sequence left) and the head
-        const int64_t Mp = w.Mpad, img = (int64_t)m->cur_B * 3 * m->S * m->S;
+        const int64_t Mp = w.Mpad, img = (int64_t)cur_B * 3 * m->S * m->S;
         struct { const char* name; void* p; int64_t n; int dt; } extra[] = {
             {"dres0", w.dres[0], Mp * m->D, 0}, {"dres1", w.dres[1], Mp * m->D, 0}, {"grad_img", w.grad_img, img, 0},   // fp32 mode only
             {"stage_adv", w.stage_adv, img, 0}, {"stage_x0", w.stage_x0, img, 0},
-            {"logits", w.logits, (int64_t)m->cur_B * m->C, 0}, {"dlogits", w.dlogits, (int64_t)m->cur_B * m->C, 0},
-            {"gscale", w.gscale, m->cur_B, 0}, {"inv_gscale", w.inv_gscale, m->cur_B, 0}, {"loss_img", w.loss_img, m->cur_B, 0},
-            {"xhat", w.xhat, (int64_t)m->cur_B * m->D, 0}, {"rstd_f", w.rstd_f, m->cur_B, 0},
+            {"logits", w.logits, (int64_t)cur_B * m->C, 0}, {"dlogits", w.dlogits, (int64_t)cur_B * m->C, 0},
+            {"gscale", w.gscale, cur_B, 0}, {"inv_gscale", w.inv_gscale, cur_B, 0}, {"loss_img", w.loss_img, cur_B, 0},
+            {"xhat", w.xhat, (int64_t)cur_B * m->D, 0}, {"rstd_f", w.rstd_f, cur_B, 0},
             {"dres_h", m->f32 ? nullptr : w.dres_h, Mp * m->D, VL_DT16}, {"dh", m->f32 ? nullptr : w.dh, Mp * m->D, VL_DT16},
             {"dctx", m->f32 ? nullptr : w.dctx, Mp * m->D, VL_DT16}, {"dqkv", m->f32 ? nullptr : w.dqkv, Mp * 3 * m->D, VL_DT16},
             {"dz", m->f32 ? nullptr : w.dz, Mp * m->MLP, VL_DT16}, {"u", m->f32 ? nullptr : w.u, Mp * 64, VL_DT16},
-            {"cls_x1", m->f32 ? nullptr : w.c.x1, (int64_t)m->cur_B * m->D, 0}, {"cls_x2", m->f32 ? nullptr : w.c.x2, (int64_t)m->cur_B * m->D, 0},
-            {"cls_ctx", m->f32 ? nullptr : w.c.ctx, (int64_t)m->cur_B * m->D, VL_DT16}};
+            {"cls_x1", m->f32 ? nullptr : w.c.x1, (int64_t)cur_B * m->D, 0}, {"cls_x2", m->f32 ? nullptr : w.c.x2, (int64_t)cur_B * m->D, 0},
+            {"cls_ctx", m->f32 ? nullptr : w.c.ctx, (int64_t)cur_B * m->D, VL_DT16}};
         for (auto& e : extra)
             if (!strcmp(what, e.name)) {
                 if (!e.p) return fail(VL_ERR_UNSUPPORTED, "%s: not in this precision mode", what);
@@ -1615,13 +1582,13 @@ int vl_debug_tensor(vl_model* m, const char* what, int layer, void** ptr, int64_
     if (m->f32) {
         if (!strcmp(what, "qkv")) { *ptr = w.f_qkv[layer]; *numel = 3 * MD; *dtype = 0; return VL_OK; }
         if (!strcmp(what, "ctx")) { *ptr = w.f_ctx[layer]; *numel = MD; *dtype = 0; return VL_OK; }
-        if (!strcmp(what, "z")) { *ptr = w.f_z[layer]; *numel = (int64_t)m->cur_B * m->T * m->MLP; *dtype = 0; return VL_OK; }
+        if (!strcmp(what, "z")) { *ptr = w.f_z[layer]; *numel = (int64_t)cur_B * m->T * m->MLP; *dtype = 0; return VL_OK; }
     } else {
         if (!strcmp(what, "qkv")) { *ptr = w.qkv[layer]; *numel = 3 * MD; *dtype = VL_DT16; return VL_OK; }
         if (!strcmp(what, "ctx")) { *ptr = w.ctx[layer]; *numel = MD; *dtype = VL_DT16; return VL_OK; }
-        if (!strcmp(what, "z")) { *ptr = w.z[layer]; *numel = (int64_t)m->cur_B * m->T * m->MLP; *dtype = VL_DT16; return VL_OK; }
+        if (!strcmp(what, "z")) { *ptr = w.z[layer]; *numel = (int64_t)cur_B * m->T * m->MLP; *dtype = VL_DT16; return VL_OK; }
     }
-    if (!strcmp(what, "lse")) { *ptr = w.lse[layer]; *numel = (int64_t)m->cur_B * m->H * m->T; *dtype = 0; return VL_OK; }
+    if (!strcmp(what, "lse")) { *ptr = w.lse[layer]; *numel = (int64_t)cur_B * m->H * m->T; *dtype = 0; return VL_OK; }
     return fail(VL_ERR_ARG, "unknown debug tensor %s", what);
 }
 

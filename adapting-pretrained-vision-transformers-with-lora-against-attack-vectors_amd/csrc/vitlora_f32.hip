@@ -23,16 +23,16 @@ GemmF32 gm(const float* A, int lda, const float* W, int ldw, int transW, int M, 
 
 // y (+)= x W^T + b (+ R), then the module's LoRA updates  y[:, rows of slot] += s * (xb A^T) B^T
 // t: [M, kext] buffer receiving the down projections (columns ext_off .. ext_off + r of each slot)
-void linear_fwd(vl_model* m, const Linear& ln, const float* x, float* t, int M, float* y, int ldy, const float* R, int ldr,
+void linear_fwd(const vl_model* m, const Pass& p, const Linear& ln, const float* x, float* t, int M, float* y, int ldy, const float* R, int ldr,
                 uint32_t stream_id, hipStream_t s) {
     GemmF32 g = gm(x, ln.in, ln.Wrun, ln.in, 0, M, ln.out, ln.in, y, ldy);
     g.bias = ln.bias; g.R = R; g.ldr = ldr;
     k_gemm_f32(g, s);
     if (ln.slots.empty() || m->cfg.lora_merged) return;
     const float* xb = x;
-    if (vl_drop_on(m)) {
-        k_mask_f32(m->ws.f_xd, x, (int64_t)M * ln.in, 0, m->drop_seed, stream_id, m->cfg.lora_dropout, s);
-        xb = m->ws.f_xd;
+    if (vl_drop_on(m, p)) {
+        k_mask_f32(p.ws.f_xd, x, (int64_t)M * ln.in, 0, m->drop_seed, stream_id, m->cfg.lora_dropout, s);
+        xb = p.ws.f_xd;
     }
     for (const Slot& sl : ln.slots) {
         GemmF32 d = gm(xb, ln.in, m->flat + sl.a_off, sl.in, 0, M, m->r, sl.in, t + sl.ext_off, ln.kext);     // t = xb A^T
@@ -44,7 +44,7 @@ void linear_fwd(vl_model* m, const Linear& ln, const float* x, float* t, int M, 
 }
 
 // dx = dy W (+ LoRA: u = dy B, dx += s * mask * (u A)); u: [M, kext]
-void linear_dgrad(vl_model* m, const Linear& ln, const float* dy, float* u, int M, float* dx, uint32_t stream_id,
+void linear_dgrad(const vl_model* m, const Pass& p, const Linear& ln, const float* dy, float* u, int M, float* dx, uint32_t stream_id,
                   hipStream_t s) {
     GemmF32 g = gm(dy, ln.out, ln.Wrun, ln.in, 1, M, ln.in, ln.out, dx, ln.in);      // W [out, in] read as [k][n]
     k_gemm_f32(g, s);
@@ -52,11 +52,11 @@ void linear_dgrad(vl_model* m, const Linear& ln, const float* dy, float* u, int 
     for (const Slot& sl : ln.slots) {
         GemmF32 d = gm(dy + sl.row_off, ln.out, m->flat + sl.b_off, m->r, 1, M, m->r, sl.out, u + sl.ext_off, ln.kext);   // u = dy B
         k_gemm_f32(d, s);
-        if (vl_drop_on(m)) {
-            GemmF32 a = gm(u + sl.ext_off, ln.kext, m->flat + sl.a_off, sl.in, 1, M, sl.in, m->r, m->ws.f_tmp, sl.in);
+        if (vl_drop_on(m, p)) {
+            GemmF32 a = gm(u + sl.ext_off, ln.kext, m->flat + sl.a_off, sl.in, 1, M, sl.in, m->r, p.ws.f_tmp, sl.in);
             a.alpha = m->scaling;
             k_gemm_f32(a, s);
-            k_mask_f32(dx, m->ws.f_tmp, (int64_t)M * sl.in, 1, m->drop_seed, stream_id, m->cfg.lora_dropout, s);
+            k_mask_f32(dx, p.ws.f_tmp, (int64_t)M * sl.in, 1, m->drop_seed, stream_id, m->cfg.lora_dropout, s);
         } else {
             GemmF32 a = gm(u + sl.ext_off, ln.kext, m->flat + sl.a_off, sl.in, 1, M, sl.in, m->r, dx, ln.in);              // dx += s u A
             a.alpha = m->scaling; a.R = dx; a.ldr = ln.in;
@@ -66,13 +66,13 @@ void linear_dgrad(vl_model* m, const Linear& ln, const float* dy, float* u, int 
 }
 
 // dB[out, r] = s * dy^T t ; dA[r, in] = s * u^T xb      (sums over the M token rows, one writer per element)
-void lora_wgrad(vl_model* m, const Linear& ln, const float* dy, const float* x, const float* t, const float* u, int M,
+void lora_wgrad(const vl_model* m, const Pass& p, const Linear& ln, const float* dy, const float* x, const float* t, const float* u, int M,
                 float* flat_grad, uint32_t stream_id, hipStream_t s) {
     if (!flat_grad || ln.slots.empty()) return;
     const float* xb = x;
-    if (vl_drop_on(m)) {
-        k_mask_f32(m->ws.f_xd, x, (int64_t)M * ln.in, 0, m->drop_seed, stream_id, m->cfg.lora_dropout, s);
-        xb = m->ws.f_xd;
+    if (vl_drop_on(m, p)) {
+        k_mask_f32(p.ws.f_xd, x, (int64_t)M * ln.in, 0, m->drop_seed, stream_id, m->cfg.lora_dropout, s);
+        xb = p.ws.f_xd;
     }
     for (const Slot& sl : ln.slots) {
         GemmF32 gb;
@@ -90,8 +90,7 @@ void lora_wgrad(vl_model* m, const Linear& ln, const float* dy, const float* x, 
 
 }  // namespace
 
-size_t f32_carve(vl_model* m, int B, int train, char* base, size_t off0) {
-    Workspace& w = m->ws;
+size_t f32_carve(const vl_model* m, Workspace& w, int train, char* base, size_t off0) {
     const int D = m->D, L = m->L, MLP = m->MLP;
     const int64_t Mpad = w.Mpad, Mppad = w.Mppad;
     size_t off = off0;
@@ -130,9 +129,8 @@ size_t f32_carve(vl_model* m, int B, int train, char* base, size_t off0) {
     return off;
 }
 
-int f32_forward(vl_model* m, const float* x, int B, int normalise, int train, hipStream_t s) {
-    (void)train;
-    Workspace& w = m->ws;
+int f32_forward(vl_model* m, Pass& p, const float* x, int B, int normalise, hipStream_t s) {
+    Workspace& w = p.ws;
     const int D = m->D, L = m->L, T = m->T, MLP = m->MLP;
     const int M = B * T, Mp = B * m->NP;
     k_patch_gather_f32(x, w.f_patches, B, m->S, m->P, normalise, m->mean, m->stdv, s);
@@ -149,22 +147,22 @@ int f32_forward(vl_model* m, const float* x, int B, int normalise, int train, hi
     for (int l = 0; l < L; ++l) {
         Layer& ly = m->layers[l];
         k_ln_fwd_f32(w.xs[2 * l], w.f_h1[l], w.mean[2 * l], w.rstd[2 * l], ly.ln1_g, ly.ln1_b, M, D, m->cfg.ln_eps, s);
-        linear_fwd(m, ly.lin[LQKV], w.f_h1[l], w.f_t[LQKV][l], M, w.f_qkv[l], 3 * D, nullptr, 0, l * 4 + LQKV, s);
+        linear_fwd(m, p, ly.lin[LQKV], w.f_h1[l], w.f_t[LQKV][l], M, w.f_qkv[l], 3 * D, nullptr, 0, l * 4 + LQKV, s);
         if (k_attn_fwd_f32(w.f_qkv[l], w.f_ctx[l], w.lse[l], B, T, m->H, D, s)) return vl_fail(VL_ERR_UNSUPPORTED, "attention: T > 224");
-        linear_fwd(m, ly.lin[LO], w.f_ctx[l], w.f_t[LO][l], M, w.xs[2 * l + 1], D, w.xs[2 * l], D, l * 4 + LO, s);
+        linear_fwd(m, p, ly.lin[LO], w.f_ctx[l], w.f_t[LO][l], M, w.xs[2 * l + 1], D, w.xs[2 * l], D, l * 4 + LO, s);
         k_ln_fwd_f32(w.xs[2 * l + 1], w.f_h2[l], w.mean[2 * l + 1], w.rstd[2 * l + 1], ly.ln2_g, ly.ln2_b, M, D, m->cfg.ln_eps, s);
-        linear_fwd(m, ly.lin[LFC1], w.f_h2[l], w.f_t[LFC1][l], M, w.f_z[l], MLP, nullptr, 0, l * 4 + LFC1, s);
+        linear_fwd(m, p, ly.lin[LFC1], w.f_h2[l], w.f_t[LFC1][l], M, w.f_z[l], MLP, nullptr, 0, l * 4 + LFC1, s);
         k_gelu_fwd_f32(w.f_z[l], w.f_a[l], (int64_t)M * MLP, s);
-        linear_fwd(m, ly.lin[LFC2], w.f_a[l], w.f_t[LFC2][l], M, w.xs[2 * l + 2], D, w.xs[2 * l + 1], D, l * 4 + LFC2, s);
+        linear_fwd(m, p, ly.lin[LFC2], w.f_a[l], w.f_t[LFC2][l], M, w.xs[2 * l + 2], D, w.xs[2 * l + 1], D, l * 4 + LFC2, s);
     }
     k_head_fwd(w.xs[2 * L], B, T, D, m->C, m->cfg.ln_eps, m->lnf_g, m->lnf_b, m->flat + m->cls_w_off,
                m->flat + m->cls_b_off, w.xhat, w.xf, w.rstd_f, w.logits, s);
     return VL_OK;
 }
 
-int f32_backward(vl_model* m, float* grad_x, float* flat_grad, hipStream_t s) {
-    Workspace& w = m->ws;
-    const int B = m->cur_B, D = m->D, L = m->L, T = m->T, MLP = m->MLP;
+int f32_backward(vl_model* m, Pass& p, float* grad_x, float* flat_grad, hipStream_t s) {
+    Workspace& w = p.ws;
+    const int B = p.B, D = m->D, L = m->L, T = m->T, MLP = m->MLP;
     const int M = B * T;
     if (flat_grad) {
         HIPCHK(hipMemsetAsync(flat_grad, 0, (size_t)m->flat_n * sizeof(float), s));
@@ -176,20 +174,20 @@ int f32_backward(vl_model* m, float* grad_x, float* flat_grad, hipStream_t s) {
     for (int l = L - 1; l >= 0; --l) {
         Layer& ly = m->layers[l];
         // MLP
-        linear_dgrad(m, ly.lin[LFC2], w.dres[cur], w.f_u, M, w.f_dz, l * 4 + LFC2, s);                  // d(a)
-        lora_wgrad(m, ly.lin[LFC2], w.dres[cur], w.f_a[l], w.f_t[LFC2][l], w.f_u, M, flat_grad, l * 4 + LFC2, s);
+        linear_dgrad(m, p, ly.lin[LFC2], w.dres[cur], w.f_u, M, w.f_dz, l * 4 + LFC2, s);                  // d(a)
+        lora_wgrad(m, p, ly.lin[LFC2], w.dres[cur], w.f_a[l], w.f_t[LFC2][l], w.f_u, M, flat_grad, l * 4 + LFC2, s);
         k_gelu_bwd_f32(w.f_dz, w.f_z[l], (int64_t)M * MLP, s);                                         // d(z) = d(a) gelu'(z)
-        linear_dgrad(m, ly.lin[LFC1], w.f_dz, w.f_u, M, w.f_dh, l * 4 + LFC1, s);
-        lora_wgrad(m, ly.lin[LFC1], w.f_dz, w.f_h2[l], w.f_t[LFC1][l], w.f_u, M, flat_grad, l * 4 + LFC1, s);
+        linear_dgrad(m, p, ly.lin[LFC1], w.f_dz, w.f_u, M, w.f_dh, l * 4 + LFC1, s);
+        lora_wgrad(m, p, ly.lin[LFC1], w.f_dz, w.f_h2[l], w.f_t[LFC1][l], w.f_u, M, flat_grad, l * 4 + LFC1, s);
         k_ln_bwd_f32(w.f_dh, w.xs[2 * l + 1], w.mean[2 * l + 1], w.rstd[2 * l + 1], ly.ln2_g, w.dres[cur], w.dres[cur ^ 1], M, D, s);
         cur ^= 1;
         // attention block
-        linear_dgrad(m, ly.lin[LO], w.dres[cur], w.f_u, M, w.f_dctx, l * 4 + LO, s);
-        lora_wgrad(m, ly.lin[LO], w.dres[cur], w.f_ctx[l], w.f_t[LO][l], w.f_u, M, flat_grad, l * 4 + LO, s);
+        linear_dgrad(m, p, ly.lin[LO], w.dres[cur], w.f_u, M, w.f_dctx, l * 4 + LO, s);
+        lora_wgrad(m, p, ly.lin[LO], w.dres[cur], w.f_ctx[l], w.f_t[LO][l], w.f_u, M, flat_grad, l * 4 + LO, s);
         if (k_attn_bwd_f32(w.f_qkv[l], w.f_ctx[l], w.f_dctx, w.lse[l], w.f_dqkv, B, T, m->H, D, s))
             return vl_fail(VL_ERR_UNSUPPORTED, "attention: T > 224");
-        linear_dgrad(m, ly.lin[LQKV], w.f_dqkv, w.f_u, M, w.f_dh, l * 4 + LQKV, s);
-        lora_wgrad(m, ly.lin[LQKV], w.f_dqkv, w.f_h1[l], w.f_t[LQKV][l], w.f_u, M, flat_grad, l * 4 + LQKV, s);
+        linear_dgrad(m, p, ly.lin[LQKV], w.f_dqkv, w.f_u, M, w.f_dh, l * 4 + LQKV, s);
+        lora_wgrad(m, p, ly.lin[LQKV], w.f_dqkv, w.f_h1[l], w.f_t[LQKV][l], w.f_u, M, flat_grad, l * 4 + LQKV, s);
         k_ln_bwd_f32(w.f_dh, w.xs[2 * l], w.mean[2 * l], w.rstd[2 * l], ly.ln1_g, w.dres[cur], w.dres[cur ^ 1], M, D, s);
         cur ^= 1;
     }
@@ -199,7 +197,7 @@ int f32_backward(vl_model* m, float* grad_x, float* flat_grad, hipStream_t s) {
         g.a_gather = 1; g.patches = m->NP;
         k_gemm_f32(g, s);
         float is[3];
-        for (int c = 0; c < 3; ++c) is[c] = m->cur_norm ? 1.f / m->stdv[c] : 1.f;
+        for (int c = 0; c < 3; ++c) is[c] = p.norm ? 1.f / m->stdv[c] : 1.f;
         k_patch_scatter_f32(w.f_tmp, grad_x, B, m->S, m->P, is, s);
     }
     return VL_OK;

@@ -727,6 +727,66 @@ def test_two_chain_attack_is_planned_away_when_switched_off_before_the_plan():
     assert torch.equal(eng2.pgd_attack(x.cuda(), y.cuda(), 8 / 255, 2 / 255, 3, random_start=True, seed=2), ref)
 
 
+def test_handle_state_after_an_attack_depends_on_the_number_of_chains():
+    """What the handle holds after vl_pgd_attack: a two-chain attack leaves no forward of the whole batch behind, so a backward
+    right after it fails with a library error and returns no gradient (VL_ERR_STATE "backward before vl_loss_ce"; before the
+    chains became explicit passes the same call got as far as launching zero-sized grids and failed with VL_ERR_HIP, so the code
+    is printed, not pinned); a one-chain attack leaves its last iteration's forward and loss, so the same call returns a
+    gradient.  Either way forward -> loss_ce -> backward afterwards gives one and the same tensor."""
+    lib_err = pkg_mod().VitLoraError
+    cfg, w, lora, x, y = make_case(image_size=64, batch=2, r=8)
+    shape = tuple(x.shape)
+    grads = {}
+    for chains in (2, 1):
+        eng = make_engine(cfg, w, lora)
+        eng.set_option("pgd_chains", chains)
+        eng.pgd_attack(x.cuda(), y.cuda(), 8 / 255, 2 / 255, 2, random_start=True, seed=3)
+        if chains == 2:
+            with pytest.raises(lib_err) as ei:
+                eng.backward(True, False, shape)
+            print("backward after a two-chain attack:", ei.value.code, ei.value)
+        else:
+            g_last, _ = eng.backward(True, False, shape)
+            assert tuple(g_last.shape) == shape and bool(torch.isfinite(g_last).all())
+        eng.forward(x.cuda(), normalise=True)
+        eng.loss_ce(y.cuda())
+        gx, _ = eng.backward(True, False, shape)
+        eng.check()
+        grads[chains] = gx.clone()
+    assert torch.equal(grads[1], grads[2])
+
+
+@pytest.mark.parametrize("prec", ["f16", "f32"])
+def test_a_size_query_does_not_disturb_results(prec):
+    """Engine.workspace_bytes (vl_plan for another batch / for training, then vl_plan of the live plan again) between two
+    takes of logits, input gradient and a 3-step attack: two identical queries return the same byte count; the query disarms
+    the handle (a plan alone does not arm a workspace: the next call is a state error, not a run on a half-planned one); and
+    once the engine has planned again, the second take equals the first bit for bit."""
+    lib_err = pkg_mod().VitLoraError
+    cfg, w, lora, x, y = make_case(image_size=64, batch=5, r=8)
+    eng = make_engine(cfg, w, lora, precision=prec)
+
+    def take():
+        logits = eng.forward(x.cuda(), normalise=True).clone()
+        eng.loss_ce(y.cuda())
+        gx, _ = eng.backward(True, False, tuple(x.shape))
+        adv = eng.pgd_attack(x.cuda(), y.cuda(), 8 / 255, 2 / 255, 3, random_start=True, seed=4).clone()
+        eng.check()
+        return logits, gx.clone(), adv
+
+    first = take()
+    sizes = [(eng.workspace_bytes(9), eng.workspace_bytes(5, True)) for _ in range(2)]
+    print("planned bytes:", sizes)
+    assert sizes[0] == sizes[1] and min(sizes[0]) > 0
+    with pytest.raises(lib_err, match="no workspace") as ei:
+        eng.forward(x.cuda(), normalise=True)
+    assert ei.value.code == -3                                        # VL_ERR_STATE
+    eng.plan(x.shape[0] + 1)                                          # a larger plan: vl_plan + vl_set_workspace
+    second = take()
+    for k, (a, b) in enumerate(zip(first, second)):
+        assert torch.equal(a, b), (prec, k, int((a != b).sum()))
+
+
 @pytest.mark.parametrize("prec", ["f16", "bf16"])
 @pytest.mark.parametrize("image_size,batch", [(64, 2), (64, 5), (224, 3), (224, 32)])
 def test_two_chain_forward_backward_equals_the_single_chain_calls(prec, image_size, batch):

@@ -211,6 +211,35 @@ def test_swin_two_chain_attack_equals_the_single_chain_attack(monkeypatch):
         assert torch.equal(outs["0"][2], outs[k][2]) and torch.equal(outs["0"][3], outs[k][3])
 
 
+def test_swin_normalisation_set_after_the_plan_reaches_the_chains(monkeypatch):
+    """vl_swin_set_normalization AFTER the chain workspaces exist (one chained attack has run): the next chained attack uses the
+    new constants -- bit for bit the result of an engine without chains under the same constants at batch 8 (4 + 4: 1/B differs
+    by a power of two), and not the result under the default constants."""
+    import ctypes as C
+    depths = (1, 1, 2, 1)
+    m = hf_swin(12, seed=41, depths=depths)
+    ab = add_lora(m, 8, 16.0, seed=42)
+    g = torch.Generator().manual_seed(43)
+    x = torch.rand(8, 3, 224, 224, generator=g).cuda()
+    y = torch.randint(0, 12, (8,), generator=g).cuda()
+    mean, std = (C.c_float * 3)(0.40, 0.50, 0.45), (C.c_float * 3)(0.30, 0.25, 0.20)
+    monkeypatch.setenv("VITLORA_SWIN_CHAIN_MIN", "2")
+    outs = {}
+    for mode in ("2", "0"):
+        monkeypatch.setenv("VITLORA_SWIN_CHAINS", mode)
+        eng = make_engine(m, 12, 8, ab, depths=depths, precision="f16")
+        default = eng.pgd_attack(x, y, 8 / 255, 2 / 255, 3, random_start=True, seed=5).clone()
+        assert eng.lib.vl_swin_set_normalization(eng.h, mean, std) == 0
+        other = eng.pgd_attack(x, y, 8 / 255, 2 / 255, 3, random_start=True, seed=5).clone()
+        eng.check()
+        torch.cuda.synchronize()
+        outs[mode] = (default.cpu(), other.cpu())
+        del eng
+    assert torch.equal(outs["2"][1], outs["0"][1]), float((outs["2"][1] != outs["0"][1]).float().mean())
+    for mode in ("2", "0"):
+        assert not torch.equal(outs[mode][0], outs[mode][1])
+
+
 def test_swin_narrow_stage_mlp_matches_hf_at_a_ragged_batch():
     """Stage 1's MLP (C = 96: fc1 -> GELU -> fc2 forward, fc2 dgrad -> * gelu' -> fc1 dgrad backward, one GEMM launch per product)
     at depths (2, 1, 1, 1) with LoRA r = 16 on fc2 and an odd batch 3 = ragged last tile, fp16:
