@@ -76,6 +76,31 @@ SIGNATURES = {
     "vl_debug_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
 }
 
+class VLGemmCase(C.Structure):
+    """vl_gemm_case of include/vitlora.h (field for field)."""
+    _fields_ = [
+        ("M", C.c_int32), ("N", C.c_int32), ("K1", C.c_int32), ("K2", C.c_int32),
+        ("epi", C.c_int32), ("bn", C.c_int32), ("Mvalid", C.c_int32), ("n_store", C.c_int32), ("k2_used", C.c_int32),
+        ("route", C.c_int32),
+        ("A1", C.c_void_p), ("W1", C.c_void_p), ("A2", C.c_void_p), ("W2", C.c_void_p),
+        ("lda1", C.c_int32), ("ldw1", C.c_int32), ("lda2", C.c_int32), ("ldw2", C.c_int32),
+        ("bias", C.c_void_p), ("C", C.c_void_p), ("C2", C.c_void_p), ("R", C.c_void_p), ("G", C.c_void_p),
+        ("ldc", C.c_int32), ("ldc2", C.c_int32), ("ldr", C.c_int32), ("ldg", C.c_int32),
+        ("pos", C.c_void_p), ("row_scale", C.c_void_p),
+        ("tokens", C.c_int32), ("patches", C.c_int32), ("grid", C.c_int32), ("psize", C.c_int32), ("img", C.c_int32),
+        ("a_gather", C.c_int32), ("inv_std", C.c_float * 3),
+        ("pgd_eps", C.c_float), ("pgd_alpha", C.c_float), ("pgd_lo", C.c_float), ("pgd_hi", C.c_float),
+        ("drop_p", C.c_float), ("drop_stream", C.c_uint32), ("drop_seed", C.c_uint64),
+        ("down_W", C.c_void_p), ("down_out", C.c_void_p),
+        ("down_ldw", C.c_int32), ("down_ld", C.c_int32), ("down_groups", C.c_int32), ("ones_col", C.c_int32),
+        ("f32_big", C.c_int32), ("transA", C.c_int32), ("transW", C.c_int32), ("Mstore", C.c_int32),
+        ("alpha", C.c_float), ("reserved", C.c_int32 * 3),
+    ]
+
+
+SIGNATURES["vl_debug_gemm"] = (C.c_int, [C.c_void_p, C.POINTER(VLGemmCase), C.c_void_p])
+
+
 class VLSwinConfig(C.Structure):
     _fields_ = [("image_size", C.c_int32), ("patch_size", C.c_int32), ("embed_dim", C.c_int32), ("depths", C.c_int32 * 4),
                 ("heads", C.c_int32 * 4), ("window", C.c_int32), ("num_labels", C.c_int32), ("ln_eps", C.c_float),

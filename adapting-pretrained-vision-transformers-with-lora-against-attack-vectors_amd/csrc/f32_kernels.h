@@ -19,7 +19,7 @@ struct GemmF32 {
     int a_gather, patches; // A row remap of the patch-embedding backward: row m reads token row m + m / patches + 1
 };
 
-void k_gemm_f32(const GemmF32& g, hipStream_t s);
+void k_gemm_f32(const GemmF32& g, hipStream_t s, int force_kernel = -1);   // force_kernel: 0 = the 64 x 64 kernel, 1 = the 128 x 128 kernel (vl_debug_gemm), -1 = by size
 void k_ln_fwd_f32(const float* x, float* h, float* mean, float* rstd, const float* g, const float* b, int M, int D,
                   float eps, hipStream_t s);
 void k_ln_bwd_f32(const float* dh, const float* x, const float* mean, const float* rstd, const float* g, const float* dres,

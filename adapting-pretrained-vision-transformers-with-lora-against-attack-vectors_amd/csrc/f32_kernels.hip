@@ -803,9 +803,10 @@ int f32_init(int device) {
     return 0;
 }
 
-void k_gemm_f32(const GemmF32& g, hipStream_t s) {
+void k_gemm_f32(const GemmF32& g, hipStream_t s, int force_kernel) {
     const double bytes = 4.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N * (g.R ? 2.0 : 1.0));
-    if (g_f32_big && g.M >= GBM && g.N >= GBN) {
+    // (both kernels guard every load and store by M / N / K: either one is correct for any shape)
+    if (force_kernel >= 0 ? force_kernel == 1 : (g_f32_big && g.M >= GBM && g.N >= GBN)) {
         ProfScope prof_("gemm_f32_big_kernel", 2.0 * g.M * (double)g.N * g.K, bytes, s);
         dim3 grid((g.N + GBN - 1) / GBN, (g.M + GBM - 1) / GBM);
         hipLaunchKernelGGL(gemm_f32_big_kernel, grid, dim3(256), 0, s, g);

@@ -88,4 +88,18 @@ int gemm_stream_set_mode(int mode);    // bit 0: streaming kernel on, bit 1: LoR
 bool gemm_stream_fuses_down(const GemmArgs& a, int epi);   // gemm_stream.hip: a.down_W = [64 rows][K1] (down_ldw), W2 / K2 = 64 the LoRA K tile, A2 unused
 bool gemm_pp_fuses_down(const GemmArgs& a, int epi);   // a.down_* set: can launch_gemm run this GEMM with the down projection inside?   // per-device kernel attributes (outside any stream capture); 0 = ok
 
+// The persistent kernels behind launch_gemm.  *_can_run: the kernel computes this shape / epilogue / argument set correctly (tile
+// multiples, pipeline depth, the epilogues it is instantiated for).  *_supports: can_run AND the process-wide switches allow it AND
+// it is the faster choice (the streaming kernel's minimum row counts, the ping-pong kernel's mode-2 depth limit): launch_gemm routes
+// by *_supports; vl_debug_gemm, which hands a chosen kernel to the tests, by *_can_run alone.
+void launch_gemm256(const GemmArgs& a, int epi, hipStream_t s);   // gemm256.hip
+bool gemm256_supports(const GemmArgs& a, int epi);                // (no worth-it part: supports == can run)
+void launch_gemm_pp(const GemmArgs& a, int epi, hipStream_t s);   // gemm_pp.hip
+bool gemm_pp_can_run(const GemmArgs& a, int epi);
+bool gemm_pp_supports(const GemmArgs& a, int epi);
+void launch_gemm_stream(const GemmArgs& a, int epi, int bn, hipStream_t s);   // gemm_stream.hip
+bool gemm_stream_can_run(const GemmArgs& a, int epi, int bn);
+bool gemm_stream_supports(const GemmArgs& a, int epi, int bn);
+void gemm_stream_set_cus(int n);  // persistent grid size of the streaming kernel
+
 }  // namespace VLNS

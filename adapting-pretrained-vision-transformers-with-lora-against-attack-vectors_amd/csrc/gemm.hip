@@ -17,15 +17,9 @@
 
 namespace VLNS {      // vl_f16 / vl_bf16: the 16-bit path is compiled once per operand type (common.h)
 
-void launch_gemm256(const GemmArgs& a, int epi, hipStream_t s);   // gemm256.hip
-bool gemm256_supports(const GemmArgs& a, int epi);
-int gemm256_init();
-void launch_gemm_pp(const GemmArgs& a, int epi, hipStream_t s);    // gemm_pp.hip
-bool gemm_pp_supports(const GemmArgs& a, int epi);
-int gemm_pp_init();
-void launch_gemm_stream(const GemmArgs& a, int epi, int bn, hipStream_t s);   // gemm_stream.hip
-bool gemm_stream_supports(const GemmArgs& a, int epi, int bn);
-int gemm_stream_init();
+int gemm256_init();        // gemm256.hip
+int gemm_pp_init();        // gemm_pp.hip
+int gemm_stream_init();    // gemm_stream.hip
 
 namespace {
 

@@ -510,26 +510,34 @@ void gemm_pp_set_cus(int n) { g_pp_cus = n; }
 int gemm_pp_mode() { return g_pp_mode; }
 void gemm_pp_set_mode(int m) { g_pp_mode = m; }
 
-bool gemm_pp_fuses_down(const GemmArgs& a, int epi) {
-    // the residual-add epilogue combines with the fused down projection only with the bias in the LoRA K tile (BC): its two row
-    // operands requested ahead leave no room for 16 bias registers
-    if (g_pp_mode == 0 || !a.down_W || gemm_small_forced()) return false;
-    if (!(epi == EPI_STORE_H16 || (epi == EPI_RESID_H16 && a.ones_col && !a.bias))) return false;
-    if (a.ones_col && epi != EPI_RESID_H16) return false;
-    if (a.down_groups < 1 || a.down_groups > 2 || a.K2 != BK || !a.W2) return false;
+// the kernel is correct for this shape, epilogue and argument set (no process-wide switch, no speed threshold)
+bool gemm_pp_can_run(const GemmArgs& a, int epi) {
+    if (a.down_W) {
+        // the residual-add epilogue combines with the fused down projection only with the bias in the LoRA K tile (BC): its two row
+        // operands requested ahead leave no room for 16 bias registers
+        if (!(epi == EPI_STORE_H16 || (epi == EPI_RESID_H16 && a.ones_col && !a.bias))) return false;
+        if (a.ones_col && epi != EPI_RESID_H16) return false;
+        if (a.down_groups < 1 || a.down_groups > 2 || a.K2 != BK || !a.W2) return false;
+        return shape_ok(a);
+    }
+    // epilogues that READ a second operand keep it in flight in registers across steps (explicit loads); the fp32 residual
+    // form does not fit the 256-register budget next to the accumulators and stays on gemm256
+    if (!(epi == EPI_STORE_H16 || epi == EPI_GELU || epi == EPI_GELU_BWD || epi == EPI_STORE_F32 || epi == EPI_NONE || epi == EPI_RESID_H16)) return false;
     return shape_ok(a);
+}
+
+bool gemm_pp_fuses_down(const GemmArgs& a, int epi) {
+    if (g_pp_mode == 0 || !a.down_W || gemm_small_forced()) return false;
+    return gemm_pp_can_run(a, epi);
 }
 
 bool gemm_pp_supports(const GemmArgs& a, int epi) {
     if (g_pp_mode == 0) return false;
     if (a.down_W) return gemm_pp_fuses_down(a, epi);
-    // epilogues that READ a second operand keep it in flight in registers across steps (explicit loads); the fp32 residual
-    // form does not fit the 256-register budget next to the accumulators and stays on gemm256
-    if (!(epi == EPI_STORE_H16 || epi == EPI_GELU || epi == EPI_GELU_BWD || epi == EPI_STORE_F32 || epi == EPI_NONE || epi == EPI_RESID_H16)) return false;
-    // measured (tools/gemm_pp_check.py, MI355X): ahead of gemm256 by 7 - 12 % on the plain 16-bit-store shapes with K <= 2304
+    // worth it: measured (tools/gemm_pp_check.py, MI355X): ahead of gemm256 by 7 - 12 % on the plain 16-bit-store shapes with K <= 2304
     // (qkv forward, o / qkv dgrad), level at K = 3072, behind on the GELU epilogues (4 helper waves carry the erf VALU)
     if (g_pp_mode == 2 && !((epi == EPI_STORE_H16 || epi == EPI_RESID_H16) && a.K1 <= g_pp_max_k)) return false;
-    return shape_ok(a);
+    return gemm_pp_can_run(a, epi);
 }
 
 int gemm_pp_init() {

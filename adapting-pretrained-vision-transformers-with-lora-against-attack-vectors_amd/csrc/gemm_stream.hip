@@ -355,22 +355,32 @@ int gemm_stream_set_mode(int mode) {
     return old;
 }
 
+void gemm_stream_set_cus(int n) { g_stream_cus = n; }
+
 // bn: 128 or 64 (the caller's column tile, as for gemm_nt_kernel)
-// a.down_W set (down_groups = 1: 64 rows, down_ldw), W2 / ldw2 / K2 = 64 the LoRA K tile, A2 unused: can the down projection
-// run inside this GEMM?
+// a.down_W set (down_groups = 1: 64 rows, down_ldw), W2 / ldw2 / K2 = 64 the LoRA K tile, A2 unused: the down projection runs
+// inside this GEMM.
+// can_run: the kernel is correct for this shape, epilogue and argument set; the minimum row counts (below them the tile kernels
+// are faster) and the on / off switches are the callers' part (gemm_stream_fuses_down / gemm_stream_supports)
+bool gemm_stream_can_run(const GemmArgs& a, int epi, int bn) {
+    if (a.a_gather || a.M % BM || a.K1 % BK || a.K1 < BK) return false;
+    if (a.down_W) {
+        if (a.down_out || bn == 64 || a.K1 + a.K2 > g_stream_max_k || a.K2 != BK || a.N % 128) return false;
+        return epi == EPI_STORE_H16 || epi == EPI_GELU_BWD;
+    }
+    if (bn == 64) return a.K2 == 0 && epi == EPI_STORE_H16 && a.N % 64 == 0;
+    if (a.K1 + a.K2 > g_stream_max_k || a.K2 % BK || a.N % 128) return false;
+    return epi == EPI_STORE_H16 || epi == EPI_GELU || epi == EPI_GELU_BWD;
+}
 bool gemm_stream_fuses_down(const GemmArgs& a, int epi) {
     if (gemm_small_forced()) return false;
-    if (!g_stream_on || !g_stream_down || a.a_gather || !a.down_W || a.down_out) return false;
-    if (a.M < g_stream_min_rows || a.M % BM || a.K1 + a.K2 > g_stream_max_k || a.K1 % BK || a.K1 < BK || a.K2 != BK || a.N % 128) return false;
-    return epi == EPI_STORE_H16 || epi == EPI_GELU_BWD;
+    if (!g_stream_on || !g_stream_down || !a.down_W) return false;
+    return a.M >= g_stream_min_rows && gemm_stream_can_run(a, epi, 128);
 }
 bool gemm_stream_supports(const GemmArgs& a, int epi, int bn) {
     if (a.down_W) return gemm_stream_fuses_down(a, epi);
-    if (!g_stream_on || a.a_gather) return false;
-    if (bn == 64) return a.M >= g_stream_min_rows64 && a.M % BM == 0 && a.K1 % BK == 0 && a.K2 == 0 && epi == EPI_STORE_H16 && a.N % 64 == 0;
-    if (a.M < g_stream_min_rows || a.M % BM || a.K1 + a.K2 > g_stream_max_k || a.K1 % BK || a.K2 % BK) return false;
-    if (a.N % 128) return false;
-    return epi == EPI_STORE_H16 || epi == EPI_GELU || epi == EPI_GELU_BWD;
+    if (!g_stream_on) return false;
+    return a.M >= (bn == 64 ? g_stream_min_rows64 : g_stream_min_rows) && gemm_stream_can_run(a, epi, bn);
 }
 
 void launch_gemm_stream(const GemmArgs& a, int epi, int bn, hipStream_t s) {

@@ -1454,11 +1454,121 @@ int vl_check_gemm(int M, int N, int K1, int K2, int epi, int pp_mode, float* max
 }
 #endif
 
+// ---- one GEMM on caller-owned buffers through a chosen kernel (tests/test_hip_gemm_ref.py: float64 reference per element) ----
+// Validates and refuses: nothing is launched unless the chosen kernel's contract holds for the case.
+int vl_debug_gemm(vl_model* m, const vl_gemm_case* c, void* stream) {
+    if (!m || !c) return fail(VL_ERR_ARG, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (m->f32) {
+        if (int rc = f32_debug_gemm(c, s)) return rc;
+        return capturing(s) ? VL_OK : check_launch("vl_debug_gemm");
+    }
+    const int epi = c->epi, bn = c->bn;
+    const bool row16 = epi == EPI_STORE_H16 || epi == EPI_GELU || epi == EPI_GELU_BWD || epi == EPI_DROP_ACC || epi == EPI_RESID_H16;
+    const bool row32 = epi == EPI_RESID_F32 || epi == EPI_STORE_F32;
+    const bool pgrad = epi == EPI_PATCH_BWD || epi == EPI_PATCH_PGD;
+    if (!(row16 || row32 || pgrad || epi == EPI_PATCH_FWD)) return fail(VL_ERR_ARG, "epi %d is not an epilogue that stores", epi);
+    if (c->route < 0 || c->route > 4) return fail(VL_ERR_ARG, "route is 0 .. 4");
+    if (!(bn == 128 || (bn == 64 && epi == EPI_STORE_H16))) return fail(VL_ERR_ARG, "bn is 128, or 64 with EPI_STORE_H16");
+    if (c->M <= 0 || c->M % 128 || c->N <= 0 || c->N % bn || c->K1 <= 0 || c->K1 % 64 || c->K2 < 0 || c->K2 % 64)
+        return fail(VL_ERR_ARG, "sizes: M %% 128, N %% bn, K1 %% 64, K2 %% 64 must be 0 (M %d N %d K1 %d K2 %d)", c->M, c->N, c->K1, c->K2);
+    const int Mvalid = c->Mvalid ? c->Mvalid : c->M;
+    if (Mvalid < 0 || Mvalid > c->M) return fail(VL_ERR_ARG, "Mvalid outside [0, M]");
+    if (c->n_store && (c->n_store < 0 || c->n_store % 16 || c->n_store >= c->N || !(row16 || row32)))
+        return fail(VL_ERR_ARG, "n_store: a multiple of 16 below N, row-layout epilogues only");
+    if (c->k2_used < 0 || c->k2_used > c->K2) return fail(VL_ERR_ARG, "k2_used outside [0, K2]");
+    const int width = c->n_store ? c->n_store : c->N;      // columns of a result row
+    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    // operands
+    const bool down = c->down_W != nullptr;
+    if (!c->A1 || !c->W1 || !c->C) return fail(VL_ERR_ARG, "A1, W1 and C are required");
+    if (c->K2 && (!c->W2 || (!down && !c->A2))) return fail(VL_ERR_ARG, "K2 > 0 needs A2 and W2");
+    if (!al16(c->A1) || !al16(c->W1) || !al16(c->A2) || !al16(c->W2) || !al16(c->bias) || !al16(c->C) || !al16(c->C2) || !al16(c->R) ||
+        !al16(c->G) || !al16(c->pos) || !al16(c->down_W) || !al16(c->down_out) || ((uintptr_t)c->row_scale & 3))
+        return fail(VL_ERR_ARG, "every base pointer must be 16-byte aligned");
+    if (c->lda1 % 8 || c->ldw1 % 8 || c->lda1 < c->K1 || c->ldw1 < c->K1) return fail(VL_ERR_ARG, "lda1 / ldw1: multiples of 8, at least K1");
+    if (c->K2 && ((!down && (c->lda2 % 8 || c->lda2 < c->K2)) || c->ldw2 % 8 || c->ldw2 < c->K2)) return fail(VL_ERR_ARG, "lda2 / ldw2: multiples of 8, at least K2");
+    if (row16 || epi == EPI_PATCH_FWD) { if (c->ldc % 8 || c->ldc < width) return fail(VL_ERR_ARG, "ldc: a multiple of 8, at least the row width"); }
+    if (row32 && (c->ldc % 4 || c->ldc < width)) return fail(VL_ERR_ARG, "ldc: a multiple of 4, at least the row width");
+    if (epi == EPI_GELU && (!c->C2 || c->ldc2 % 8 || c->ldc2 < width)) return fail(VL_ERR_ARG, "EPI_GELU needs C2 (ldc2 a multiple of 8, at least the row width)");
+    if (epi == EPI_GELU_BWD || epi == EPI_RESID_H16 || epi == EPI_DROP_ACC) {
+        if (!c->R || c->ldr % 8 || c->ldr < width) return fail(VL_ERR_ARG, "this epilogue needs R (h16; ldr a multiple of 8, at least the row width)");
+    }
+    if (epi == EPI_RESID_F32 && (!c->R || c->ldr % 4 || c->ldr < width)) return fail(VL_ERR_ARG, "EPI_RESID_F32 needs R (f32; ldr a multiple of 4, at least the row width)");
+    if (epi == EPI_DROP_ACC) {
+        if (!(c->drop_p >= 0.f && c->drop_p < 1.f)) return fail(VL_ERR_ARG, "drop_p outside [0, 1)");
+        if (c->G && (c->ldg % 8 || c->ldg < width)) return fail(VL_ERR_ARG, "ldg: a multiple of 8, at least the row width");
+    }
+    // patch geometry
+    if (epi == EPI_PATCH_FWD || pgrad || c->a_gather) {
+        if (c->patches <= 0 || c->tokens != c->patches + 1 || Mvalid % c->patches) return fail(VL_ERR_ARG, "patch geometry: tokens = patches + 1, Mvalid a multiple of patches");
+    }
+    if (epi == EPI_PATCH_FWD && !c->pos) return fail(VL_ERR_ARG, "EPI_PATCH_FWD needs pos");
+    if (pgrad) {
+        if (c->grid <= 0 || c->grid * c->grid != c->patches || c->psize <= 0 || c->psize % 4 || c->img != c->grid * c->psize || c->N != 3 * c->psize * c->psize)
+            return fail(VL_ERR_ARG, "patch gradient: patches = grid^2, psize %% 4 = 0, img = grid * psize, N = 3 psize^2");
+        if (epi == EPI_PATCH_PGD && !c->R) return fail(VL_ERR_ARG, "EPI_PATCH_PGD needs R (x0)");
+    }
+    // LoRA down projection inside the GEMM
+    if (down) {
+        if (c->K2 != 64 || c->down_ldw % 8 || c->down_ldw < c->K1 || c->down_groups < 1 || c->down_groups > 2 || c->n_store || c->a_gather)
+            return fail(VL_ERR_ARG, "fused down projection: K2 = 64, down_ldw a multiple of 8 at least K1, down_groups 1 or 2");
+        if (c->down_out && (c->down_ld % 8 || c->down_ld < 64)) return fail(VL_ERR_ARG, "down_ld: a multiple of 8, at least 64");
+        if (c->ones_col && c->bias) return fail(VL_ERR_ARG, "ones_col: the bias sits in column 63 of W2, `bias` must be NULL");
+    } else if (c->ones_col || c->down_out) return fail(VL_ERR_ARG, "ones_col / down_out without down_W");
+
+    GemmArgs g = gemm_args((const h16*)c->A1, c->lda1, (const h16*)c->W1, c->ldw1, c->K1, c->M, c->N);
+    if (c->K2) add_ext(g, down ? nullptr : (const h16*)c->A2, c->lda2, (const h16*)c->W2, c->ldw2, c->K2);
+    g.Mvalid = Mvalid; g.n_store = c->n_store; g.k2_used = c->k2_used;
+    g.bias = c->bias; g.C = c->C; g.ldc = c->ldc; g.C2 = c->C2; g.ldc2 = c->ldc2; g.R = c->R; g.ldr = c->ldr;
+    g.pos = c->pos; g.tokens = c->tokens; g.patches = c->patches; g.grid = c->grid; g.psize = c->psize; g.img = c->img;
+    for (int k = 0; k < 3; ++k) g.inv_std[k] = c->inv_std[k];
+    g.row_scale = c->row_scale; g.err_flag = pgrad ? m->err_flag : nullptr;
+    g.pgd_eps = c->pgd_eps; g.pgd_alpha = c->pgd_alpha; g.pgd_lo = c->pgd_lo; g.pgd_hi = c->pgd_hi;
+    g.a_gather = c->a_gather ? 1 : 0;
+    g.G = (const h16*)c->G; g.ldg = c->ldg;
+    g.drop_seed = c->drop_seed; g.drop_stream = c->drop_stream; g.drop_p = c->drop_p; g.drop_inv_keep = 1.f / (1.f - c->drop_p);
+    if (down) {
+        g.down_W = (const h16*)c->down_W; g.down_ldw = c->down_ldw; g.down_out = (h16*)c->down_out; g.down_ld = c->down_ld;
+        g.down_groups = c->down_groups; g.ones_col = c->ones_col ? 1 : 0;
+    }
+    if (gemm_init(m->device)) return fail(VL_ERR_HIP, "gemm_init failed");
+    const bool narrow = g.n_store > 0;
+    switch (c->route) {
+        case 0:
+            // launch_gemm aborts when a fused-down argument set falls through to the 128-row kernel: turn that away here
+            if (down && !gemm_stream_fuses_down(g, epi) && !(bn != 64 && !gemm_small_forced() && gemm_pp_supports(g, epi)))
+                return fail(VL_ERR_UNSUPPORTED, "no kernel launch_gemm would pick runs this fused down projection");
+            launch_gemm(g, epi, bn, s);
+            break;
+        case 1: {
+            if (down) return fail(VL_ERR_UNSUPPORTED, "the 128-row kernel has no fused down projection");
+            struct Restore { int keep; ~Restore() { gemm_force_small(keep); } } restore{gemm_force_small(1)};
+            launch_gemm(g, epi, bn, s);
+            break;
+        }
+        case 2:
+            if (bn != 128 || narrow || down || !gemm256_supports(g, epi)) return fail(VL_ERR_UNSUPPORTED, "the 256-row kernel cannot run this case");
+            launch_gemm256(g, epi, s);
+            break;
+        case 3:
+            if (bn != 128 || narrow || !gemm_pp_can_run(g, epi)) return fail(VL_ERR_UNSUPPORTED, "the ping-pong kernel cannot run this case");
+            launch_gemm_pp(g, epi, s);
+            break;
+        case 4:
+            if (!gemm_stream_can_run(g, epi, bn)) return fail(VL_ERR_UNSUPPORTED, "the streaming kernel cannot run this case");
+            launch_gemm_stream(g, epi, bn, s);
+            break;
+    }
+    if (!capturing(s)) return check_launch("vl_debug_gemm");
+    return VL_OK;
+}
+
 // persistent-grid size of the GEMM kernels (and the batch threshold of the per-image attention form of `m`, if given):
 // experiments with two half-batch chains on disjoint halves of the chip (tools/dual_chain_probe.py)
 int vl_debug_set_cus(vl_model* m, int cus) {
     if (cus <= 0) return fail(VL_ERR_ARG, "cus must be positive");
-    gemm256_set_cus(cus); gemm_pp_set_cus(cus);
+    gemm256_set_cus(cus); gemm_pp_set_cus(cus); gemm_stream_set_cus(cus);
     if (m) m->num_cus = cus;
     return VL_OK;
 }

@@ -88,7 +88,34 @@ void lora_wgrad(const vl_model* m, const Pass& p, const Linear& ln, const float*
     }
 }
 
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 }  // namespace
+
+// vl_debug_gemm on an fp32 handle: GemmF32's contract (f32_kernels.h) checked, then one launch of the chosen kernel
+int f32_debug_gemm(const vl_gemm_case* c, hipStream_t s) {
+    if (c->M <= 0 || c->N <= 0 || c->K1 <= 0 || c->K2 != 0) return vl_fail(VL_ERR_ARG, "fp32 GEMM: M, N, K1 positive, K2 = 0");
+    if (c->N % 4 || c->K1 % 4 || (c->transA && c->M % 4)) return vl_fail(VL_ERR_ARG, "fp32 GEMM: N, K (and M when transA) must be multiples of 4");
+    if (c->f32_big < 0 || c->f32_big > 1 || c->route != 0) return vl_fail(VL_ERR_ARG, "fp32 GEMM: f32_big is 0 or 1, route 0");
+    if (!c->A1 || !c->W1 || !c->C) return vl_fail(VL_ERR_ARG, "fp32 GEMM: null operand");
+    if (!aligned16(c->A1) || !aligned16(c->W1) || !aligned16(c->C) || !aligned16(c->bias) || !aligned16(c->R))
+        return vl_fail(VL_ERR_ARG, "fp32 GEMM: every base pointer must be 16-byte aligned");
+    const int Mstore = c->Mstore ? c->Mstore : c->M;
+    if (Mstore < 0 || Mstore > c->M) return vl_fail(VL_ERR_ARG, "fp32 GEMM: Mstore outside [0, M]");
+    if (c->lda1 % 4 || c->ldw1 % 4 || c->ldc % 4 || (c->R && c->ldr % 4)) return vl_fail(VL_ERR_ARG, "fp32 GEMM: every row pitch must be a multiple of 4 elements");
+    if (c->lda1 < (c->transA ? c->M : c->K1) || c->ldw1 < (c->transW ? c->N : c->K1) || c->ldc < c->N || (c->R && c->ldr < c->N))
+        return vl_fail(VL_ERR_ARG, "fp32 GEMM: a row pitch is below the row width");
+    if (c->a_gather && (c->patches <= 0 || c->transA)) return vl_fail(VL_ERR_ARG, "fp32 GEMM: a_gather needs patches > 0 and a non-transposed A");
+    GemmF32 g;
+    memset(&g, 0, sizeof g);
+    g.A = (const float*)c->A1; g.lda = c->lda1; g.transA = c->transA ? 1 : 0;
+    g.W = (const float*)c->W1; g.ldw = c->ldw1; g.transW = c->transW ? 1 : 0;
+    g.M = c->M; g.N = c->N; g.K = c->K1; g.Mstore = Mstore; g.alpha = c->alpha;
+    g.bias = c->bias; g.R = (const float*)c->R; g.ldr = c->ldr; g.C = (float*)c->C; g.ldc = c->ldc;
+    g.a_gather = c->a_gather ? 1 : 0; g.patches = c->patches;
+    k_gemm_f32(g, s, c->f32_big);
+    return VL_OK;
+}
 
 size_t f32_carve(const vl_model* m, Workspace& w, int train, char* base, size_t off0) {
     const int D = m->D, L = m->L, MLP = m->MLP;

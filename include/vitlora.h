@@ -315,7 +315,7 @@ int vl_debug_set_gemm_stream(int mode);
  * and the backward after it run such batches as the same two chains -- the adversarial-patch EoT step goes through these calls;
  * vl_debug_tensor then does not see the activations).  Results are bit-identical either way. */
 int vl_debug_set_option(vl_model* m, const char* name, int value);
-int vl_debug_set_cus(vl_model* m, int cus);   /* persistent GEMM grid size (diagnostic; default = the device's CU count) */
+int vl_debug_set_cus(vl_model* m, int cus);   /* grid size of the persistent GEMM kernels -- 256-row, ping-pong, streaming (diagnostic; default = the device's CU count) */
 
 /* Introspection for tests / profiling.  vl_debug_counter: "graph_captures" = PGD graphs captured so far,
  * "commits" = vl_lora_commit executions, "dirty" = 1 if parameters changed since the last commit, "lds_poisons" = launches of the
@@ -323,6 +323,55 @@ int vl_debug_set_cus(vl_model* m, int cus);   /* persistent GEMM grid size (diag
  * LDS with NaN patterns; results must not change -- process-wide, attacks then run without the graph). */
 int vl_debug_counter(vl_model* m, const char* what, int64_t* value);
 int vl_debug_tensor(vl_model* m, const char* what, int layer, void** ptr, int64_t* numel, int* dtype);
+
+/* One GEMM on CALLER-OWNED device buffers through one chosen kernel with one chosen epilogue (tests/test_hip_gemm_ref.py compares
+ * the result element by element with a float64 reference; vl_check_gemm above only compares kernels with each other).
+ * The handle's precision selects the operand type: VL_PREC_F16 / VL_PREC_BF16 run the 16-bit kernels of csrc/gemm.h
+ *   C[M,N] = A1[M,K1] W1[N,K1]^T + A2[M,K2] W2[N,K2]^T + bias, then the epilogue `epi` (GemmEpilogue of csrc/gemm.h),
+ * VL_PREC_F32 runs k_gemm_f32:  C = alpha * op(A1) op(W1) + bias + R  (K = K1; the fields marked "f32").
+ * The entry VALIDATES AND REFUSES: null required pointers, base pointers or row pitches that are not 16-byte aligned, pitches below
+ * the row width, sizes that are not the multiples the kernels need (M % 128, N % bn, K % 64, n_store % 16; fp32: K % 4, N % 4,
+ * M % 4 when transA) give VL_ERR_ARG; a forced route whose kernel cannot run the shape / epilogue / argument set gives
+ * VL_ERR_UNSUPPORTED.  Nothing is launched then.  Buffer SIZES are the caller's: every operand holds M (W: N) rows of its pitch.
+ * A forced route bypasses the thresholds that only pick the faster kernel (the streaming kernel's minimum row counts, the
+ * ping-pong kernel's depth limit) and nothing else.  Only enqueues on `stream`: no allocation, no synchronisation. */
+typedef struct vl_gemm_case {
+    int32_t M, N, K1, K2;
+    int32_t epi;          /* GemmEpilogue value (not EPI_NONE) */
+    int32_t bn;           /* column tile: 128, or 64 (skinny form, EPI_STORE_H16 only) */
+    int32_t Mvalid;       /* rows the patch epilogues may store / gather (0 = M) */
+    int32_t n_store;      /* 0, or leading columns stored (multiple of 16, < N; row-layout epilogues; routes 0, 1, 4) */
+    int32_t k2_used;      /* nonzero columns of the LoRA K tile (0 = unknown: all of them) */
+    int32_t route;        /* 0 = what launch_gemm picks, 1 = 128-row kernel, 2 = 256-row persistent, 3 = ping-pong, 4 = streaming */
+    const void* A1; const void* W1; const void* A2; const void* W2;     /* 16-bit operands (f32 handle: fp32 A1, W1) */
+    int32_t lda1, ldw1, lda2, ldw2;                                     /* pitches in elements */
+    const float* bias;    /* [N] or NULL */
+    void* C; void* C2;    /* C2: gelu'(z) of EPI_GELU */
+    const void* R;        /* residual / saved gelu'(z) / x0 of EPI_PATCH_PGD (may alias C for EPI_RESID_F32 and on an f32 handle) */
+    const void* G;        /* EPI_DROP_ACC: optional extra factor */
+    int32_t ldc, ldc2, ldr, ldg;
+    const float* pos;     /* EPI_PATCH_FWD: position embedding [tokens][ldc] */
+    const float* row_scale;   /* EPI_PATCH_BWD / EPI_PATCH_PGD: per-image factor or NULL */
+    int32_t tokens, patches, grid, psize, img;      /* patch geometry: tokens = patches + 1, patches = grid^2, img = grid * psize */
+    int32_t a_gather;     /* A row m reads row m + m / patches + 1 (the non-CLS token rows); f32 handle too */
+    float inv_std[3];
+    float pgd_eps, pgd_alpha, pgd_lo, pgd_hi;
+    float drop_p;         /* EPI_DROP_ACC: mask = drop_scale(drop_seed, drop_stream, m * N + n) of csrc/common.h */
+    uint32_t drop_stream;
+    uint64_t drop_seed;
+    /* LoRA down projection inside the GEMM (routes 0, 3, 4): t = A1 down_W^T, down_W = [64 rows][K1] zero padded, K2 = 64, A2 unused */
+    const void* down_W; void* down_out;     /* down_out: receives t [M][64] (ping-pong kernel; must be NULL for the streaming kernel) */
+    int32_t down_ldw, down_ld, down_groups; /* 16-column groups of t in use: 1 or 2 */
+    int32_t ones_col;     /* EPI_RESID_H16 with the down projection inside: column 63 of W2 holds the bias, `bias` NULL */
+    /* f32 handle (GemmF32 of csrc/f32_kernels.h) */
+    int32_t f32_big;      /* 0: the 64 x 64 kernel, 1: the 128 x 128 kernel */
+    int32_t transA, transW;
+    int32_t Mstore;       /* rows >= Mstore are computed, not stored (0 = M) */
+    float alpha;
+    int32_t reserved[3];
+} vl_gemm_case;
+/* The patch-gradient epilogues flag a non-finite gradient in the handle's error word: vl_check_errors reports it. */
+int vl_debug_gemm(vl_model* m, const vl_gemm_case* c, void* stream);
 
 #ifdef __cplusplus
 }
