@@ -101,6 +101,23 @@ class VLGemmCase(C.Structure):
 SIGNATURES["vl_debug_gemm"] = (C.c_int, [C.c_void_p, C.POINTER(VLGemmCase), C.c_void_p])
 
 
+class VLAttnCase(C.Structure):
+    """vl_attn_case of include/vitlora.h (field for field)."""
+    _fields_ = [
+        ("B", C.c_int32), ("T", C.c_int32), ("H", C.c_int32), ("kernel", C.c_int32),
+        ("qkv", C.c_void_p), ("ctx", C.c_void_p), ("lse", C.c_void_p), ("dctx", C.c_void_p), ("dqkv", C.c_void_p),
+        ("down_W", C.c_void_p), ("down_out", C.c_void_p),
+        ("r", C.c_int32), ("mods", C.c_uint32), ("reserved", C.c_int32 * 4),
+    ]
+
+
+# vl_attn_case.kernel (the VL_ATTN_* values of include/vitlora.h)
+ATTN_KERNELS = {"fwd": 0, "bwd": 1, "img_fwd": 2, "img_bwd": 3, "ring_bwd": 4, "cls_fwd": 5, "cls_bwd": 6,
+                "f32_mfma_fwd": 7, "f32_mfma_bwd": 8, "f32_scalar_fwd": 9, "f32_scalar_bwd": 10}
+
+SIGNATURES["vl_debug_attention"] = (C.c_int, [C.c_void_p, C.POINTER(VLAttnCase), C.c_void_p])
+
+
 class VLSwinConfig(C.Structure):
     _fields_ = [("image_size", C.c_int32), ("patch_size", C.c_int32), ("embed_dim", C.c_int32), ("depths", C.c_int32 * 4),
                 ("heads", C.c_int32 * 4), ("window", C.c_int32), ("num_labels", C.c_int32), ("ln_eps", C.c_float),

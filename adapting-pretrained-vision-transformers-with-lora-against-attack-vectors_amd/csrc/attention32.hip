@@ -1438,9 +1438,9 @@ void launch_fwd_img(const h16* qkv, h16* ctx, float* lse2, int B, int T, int H, 
 int g_attn_ring = 1;      // VITLORA_ATTN_RING=0: the two-phase per-image backward (attn_bwd_img_kernel)
 template <int NT>
 void launch_bwd_img(const h16* qkv, const h16* ctx, const h16* dctx, const float* lse2, h16* dqkv, int B, int T, int H, int D,
-                    const LoraDown& lo, hipStream_t s) {
+                    const LoraDown& lo, bool ring, hipStream_t s) {
     const float scale = 0.125f;
-    if (g_attn_ring && T <= ring_img_rows<NT>()) {
+    if (ring) {
         hipLaunchKernelGGL((attn_bwd_ring_kernel<NT>), dim3(B), dim3(64 * IMG_WAVES), bwd_ring_lds<NT>(), s, qkv, ctx, dctx, lse2, dqkv,
                            T, H, D, scale, scale * 1.4426950408889634f, lo);
         return;
@@ -1522,16 +1522,18 @@ int k_attention_img_fwd(const h16* qkv, h16* ctx, float* lse2, int B, int T, int
     return 0;
 }
 int k_attention_img_bwd(const h16* qkv, const h16* ctx, const h16* dctx, const float* lse2, h16* dqkv, int B, int T, int H, int D,
-                        const h16* Bd, h16* u, int r, unsigned mods, hipStream_t s) {
-    const bool ring = g_attn_ring && T <= (T <= 32 ? ring_img_rows<1>() : ring_img_rows<7>());      // the kernel launch_bwd_img picks
+                        const h16* Bd, h16* u, int r, unsigned mods, hipStream_t s, int force_ring) {
+    const int ring_rows = T <= 32 ? ring_img_rows<1>() : ring_img_rows<7>();
+    if (force_ring == 1 && T > ring_rows) return -1;
+    const bool ring = force_ring >= 0 ? force_ring == 1 : g_attn_ring && T <= ring_rows;
     // executed: the ring form issues 5 products per 32 x 32 tile pair (S, dP, dV, dK, dQ), the two-phase form 7 (S and dP twice)
     ProfScope prof_(ring ? "attn_bwd_ring_kernel" : "attn_bwd_img_kernel", 10.0 * B * H * (double)T * T * HD, (double)B * T * D * 16.0, s,
                     (ring ? 10.0 : 14.0) * B * H * (double)TPAD(T) * TPAD(T) * HD);
     LoraDown lo;
     lo.W = Bd; lo.out = u; lo.r = r; lo.mods = mods;
     if (!Bd || !u || r <= 0 || r > 8 || !mods) { lo.W = nullptr; lo.out = nullptr; }
-    if (T <= 32) launch_bwd_img<1>(qkv, ctx, dctx, lse2, dqkv, B, T, H, D, lo, s);
-    else if (T <= 224) launch_bwd_img<7>(qkv, ctx, dctx, lse2, dqkv, B, T, H, D, lo, s);
+    if (T <= 32) launch_bwd_img<1>(qkv, ctx, dctx, lse2, dqkv, B, T, H, D, lo, ring, s);
+    else if (T <= 224) launch_bwd_img<7>(qkv, ctx, dctx, lse2, dqkv, B, T, H, D, lo, ring, s);
     else return -1;
     return 0;
 }

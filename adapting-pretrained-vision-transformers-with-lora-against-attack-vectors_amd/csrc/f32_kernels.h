@@ -30,8 +30,9 @@ void k_mask_f32(float* dst, const float* src, int64_t n, int add, uint64_t seed,
 void k_patch_gather_f32(const float* x, float* out, int B, int S, int P, int normalise, const float* mean, const float* std,
                         hipStream_t s);
 void k_patch_scatter_f32(const float* dp, float* gx, int B, int S, int P, const float inv_std[3], hipStream_t s);
-int k_attn_fwd_f32(const float* qkv, float* ctx, float* lse, int B, int T, int H, int D, hipStream_t s);
+// force_mfma: 1 = the MFMA kernel, 0 = the scalar kernel (vl_debug_attention), -1 = the process-wide switch
+int k_attn_fwd_f32(const float* qkv, float* ctx, float* lse, int B, int T, int H, int D, hipStream_t s, int force_mfma = -1);
 int k_attn_bwd_f32(const float* qkv, const float* ctx, const float* dctx, const float* lse, float* dqkv, int B, int T, int H,
-                   int D, hipStream_t s);
+                   int D, hipStream_t s, int force_mfma = -1);
 
 }  // namespace VLNS

@@ -853,9 +853,9 @@ void k_patch_scatter_f32(const float* dp, float* gx, int B, int S, int P, const 
     hipLaunchKernelGGL(patch_scatter_f32_kernel, dim3(nblk((int64_t)B * 3 * S * S, 256, 8192)), dim3(256), 0, s, dp, gx, B,
                        S, P, G, inv_std[0], inv_std[1], inv_std[2]);
 }
-int k_attn_fwd_f32(const float* qkv, float* ctx, float* lse, int B, int T, int H, int D, hipStream_t s) {
+int k_attn_fwd_f32(const float* qkv, float* ctx, float* lse, int B, int T, int H, int D, hipStream_t s, int force_mfma) {
     if (T > ATMAX) return -1;
-    if (g_f32_attn_mfma) {
+    if (force_mfma >= 0 ? force_mfma == 1 : g_f32_attn_mfma != 0) {
         ProfScope prof_("attn_fwd_f32_mfma_kernel", 4.0 * B * H * (double)T * T * AHD, (double)B * T * D * 16.0, s);
         hipLaunchKernelGGL(attn_fwd_f32_mfma_kernel, dim3(B * H), dim3(256), attn_mfma_lds_bytes(T), s, qkv, ctx, lse, T, H, D);
         return 0;
@@ -865,9 +865,9 @@ int k_attn_fwd_f32(const float* qkv, float* ctx, float* lse, int B, int T, int H
     return 0;
 }
 int k_attn_bwd_f32(const float* qkv, const float* ctx, const float* dctx, const float* lse, float* dqkv, int B, int T, int H,
-                   int D, hipStream_t s) {
+                   int D, hipStream_t s, int force_mfma) {
     if (T > ATMAX) return -1;
-    if (g_f32_attn_mfma) {
+    if (force_mfma >= 0 ? force_mfma == 1 : g_f32_attn_mfma != 0) {
         ProfScope prof_("attn_bwd_f32_mfma_kernel", 10.0 * B * H * (double)T * T * AHD, (double)B * T * D * 32.0, s);
         hipLaunchKernelGGL(attn_bwd_f32_mfma_kernel, dim3(B * H), dim3(256), attn_mfma_lds_bytes(T), s, qkv, ctx, dctx, lse, dqkv, T, H, D);
         return 0;

@@ -76,8 +76,10 @@ int k_attention32_bwd(const h16* qkv, const h16* ctx, const h16* dctx, const flo
 // per-image persistent forms with the LoRA down projection fused in (attention32.hip); Ad / Bd == nullptr: attention only
 int k_attention_img_fwd(const h16* qkv, h16* ctx, float* lse2, int B, int T, int H, int D, const h16* Ad, h16* t, int r,
                         hipStream_t s);
+// force_ring: -1 = the process-wide switch and T pick the kernel (the product), 1 = the ring kernel (T <= 200, else -1 is returned),
+// 0 = the two-phase kernel (vl_debug_attention)
 int k_attention_img_bwd(const h16* qkv, const h16* ctx, const h16* dctx, const float* lse2, h16* dqkv, int B, int T, int H,
-                        int D, const h16* Bd, h16* u, int r, unsigned mods, hipStream_t s);
+                        int D, const h16* Bd, h16* u, int r, unsigned mods, hipStream_t s, int force_ring = -1);
 
 // cls_path.hip: the last encoder layer on CLS rows only (compact [B, D] buffers)
 int k_attn_cls_fwd(const h16* qkv, h16* ctx_c, float* lse_c, int B, int T, int H, int D, hipStream_t s);

@@ -176,11 +176,13 @@ static inline int f32_forward(vl_model*, Pass&, const float*, int, int, hipStrea
 static inline int f32_backward(vl_model*, Pass&, float*, float*, hipStream_t) { return VL_ERR_STATE; }
 static inline int f32_init(int) { return 0; }
 static inline int f32_debug_gemm(const vl_gemm_case*, hipStream_t) { return VL_ERR_STATE; }
+static inline int f32_debug_attention(const vl_attn_case*, hipStream_t) { return VL_ERR_STATE; }
 #else
 size_t f32_carve(const vl_model* m, Workspace& w, int train, char* base, size_t off0);      // w.Mpad / w.Mppad are set by the caller
 int f32_forward(vl_model* m, Pass& p, const float* x, int B, int normalise, hipStream_t s);  // p.train / p.rows are set by the caller
 int f32_backward(vl_model* m, Pass& p, float* grad_x, float* flat_grad, hipStream_t s);
 int f32_init(int device);     // kernel attributes; 0 = ok
 int f32_debug_gemm(const vl_gemm_case* c, hipStream_t s);   // vl_debug_gemm on an fp32 handle: validates, then one k_gemm_f32
+int f32_debug_attention(const vl_attn_case* c, hipStream_t s);   // vl_debug_attention on an fp32 handle (validated by the caller): one fp32 attention kernel
 #endif
 }  // namespace VLNS

@@ -1564,6 +1564,59 @@ int vl_debug_gemm(vl_model* m, const vl_gemm_case* c, void* stream) {
     return VL_OK;
 }
 
+// ---- one attention kernel on caller-owned buffers, named explicitly (tests/test_hip_attn_ref.py: float64 reference per element) ----
+// Validates and refuses like vl_debug_gemm.  The per-device kernel attributes were set by vl_create (attention32_init / f32_init).
+int vl_debug_attention(vl_model* m, const vl_attn_case* c, void* stream) {
+    if (!m || !c) return fail(VL_ERR_ARG, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    const int k = c->kernel;
+    if (k < VL_ATTN_FWD || k > VL_ATTN_F32_SCALAR_BWD) return fail(VL_ERR_ARG, "unknown attention kernel %d", k);
+    const bool f32k = k >= VL_ATTN_F32_MFMA_FWD;
+    if (f32k != (m->f32 != 0)) return fail(VL_ERR_ARG, "attention kernel %d does not belong to this handle's precision", k);
+    const bool bwd = k == VL_ATTN_BWD || k == VL_ATTN_IMG_BWD || k == VL_ATTN_RING_BWD || k == VL_ATTN_CLS_BWD || k == VL_ATTN_F32_MFMA_BWD ||
+                     k == VL_ATTN_F32_SCALAR_BWD;
+    const bool has_down = k == VL_ATTN_IMG_FWD || k == VL_ATTN_IMG_BWD || k == VL_ATTN_RING_BWD;
+    const bool cls = k == VL_ATTN_CLS_FWD || k == VL_ATTN_CLS_BWD;
+    if (c->B < 1 || c->H < 1 || c->T < 2) return fail(VL_ERR_ARG, "attention: B >= 1, H >= 1, T >= 2 (B %d T %d H %d)", c->B, c->T, c->H);
+    if (!c->qkv || !c->ctx || !c->lse || (bwd && (!c->dctx || !c->dqkv))) return fail(VL_ERR_ARG, "attention: null operand");
+    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    if (!al16(c->qkv) || !al16(c->ctx) || !al16(c->lse) || !al16(c->dctx) || !al16(c->dqkv) || !al16(c->down_W) || !al16(c->down_out))
+        return fail(VL_ERR_ARG, "attention: every pointer must be 16-byte aligned");
+    const bool down = c->down_W != nullptr;
+    if (down) {
+        if (!c->down_out) return fail(VL_ERR_ARG, "attention: down_W without down_out");
+        if (c->r < 1 || c->r > 8) return fail(VL_ERR_ARG, "attention: r is 1 .. 8");
+        if (bwd && (c->mods < 1u || c->mods > 7u)) return fail(VL_ERR_ARG, "attention: mods is 1 .. 7");
+        if (!has_down) return fail(VL_ERR_UNSUPPORTED, "attention kernel %d has no fused down projection", k);
+    } else if (c->down_out) return fail(VL_ERR_ARG, "attention: down_out without down_W");
+    const int tmax = cls ? 256 : k == VL_ATTN_RING_BWD ? 200 : 224;
+    if (c->T > tmax) return fail(VL_ERR_UNSUPPORTED, "attention kernel %d: T %d above its limit %d", k, c->T, tmax);
+    const int B = c->B, T = c->T, H = c->H, D = 64 * c->H;
+    int rc = 0;
+    if (f32k) {
+        rc = f32_debug_attention(c, s);
+    } else {
+        const h16* qkv = (const h16*)c->qkv;
+        h16* ctx = (h16*)c->ctx;
+        const h16* dctx = (const h16*)c->dctx;
+        h16* dqkv = (h16*)c->dqkv;
+        const h16* W = (const h16*)c->down_W;
+        h16* out = (h16*)c->down_out;
+        switch (k) {
+            case VL_ATTN_FWD: rc = k_attention32_fwd(qkv, ctx, c->lse, B, T, H, D, s); break;
+            case VL_ATTN_BWD: rc = k_attention32_bwd(qkv, ctx, dctx, c->lse, dqkv, B, T, H, D, s); break;
+            case VL_ATTN_IMG_FWD: rc = k_attention_img_fwd(qkv, ctx, c->lse, B, T, H, D, W, out, c->r, s); break;
+            case VL_ATTN_IMG_BWD: rc = k_attention_img_bwd(qkv, ctx, dctx, c->lse, dqkv, B, T, H, D, W, out, c->r, c->mods, s, 0); break;
+            case VL_ATTN_RING_BWD: rc = k_attention_img_bwd(qkv, ctx, dctx, c->lse, dqkv, B, T, H, D, W, out, c->r, c->mods, s, 1); break;
+            case VL_ATTN_CLS_FWD: rc = k_attn_cls_fwd(qkv, ctx, c->lse, B, T, H, D, s); break;
+            case VL_ATTN_CLS_BWD: rc = k_attn_cls_bwd(qkv, ctx, dctx, c->lse, dqkv, B, T, H, D, s); break;
+        }
+    }
+    if (rc) return fail(VL_ERR_UNSUPPORTED, "attention kernel %d refused T %d", k, T);
+    if (!capturing(s)) return check_launch("vl_debug_attention");
+    return VL_OK;
+}
+
 // persistent-grid size of the GEMM kernels (and the batch threshold of the per-image attention form of `m`, if given):
 // experiments with two half-batch chains on disjoint halves of the chip (tools/dual_chain_probe.py)
 int vl_debug_set_cus(vl_model* m, int cus) {

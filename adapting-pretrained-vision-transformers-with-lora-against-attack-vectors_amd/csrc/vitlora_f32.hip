@@ -117,6 +117,16 @@ int f32_debug_gemm(const vl_gemm_case* c, hipStream_t s) {
     return VL_OK;
 }
 
+// vl_debug_attention on an fp32 handle (the caller validated the case): one launch of the named fp32 attention kernel
+int f32_debug_attention(const vl_attn_case* c, hipStream_t s) {
+    const int D = 64 * c->H;
+    const int mfma = c->kernel == VL_ATTN_F32_MFMA_FWD || c->kernel == VL_ATTN_F32_MFMA_BWD;
+    if (c->kernel == VL_ATTN_F32_MFMA_FWD || c->kernel == VL_ATTN_F32_SCALAR_FWD)
+        return k_attn_fwd_f32((const float*)c->qkv, (float*)c->ctx, c->lse, c->B, c->T, c->H, D, s, mfma);
+    return k_attn_bwd_f32((const float*)c->qkv, (const float*)c->ctx, (const float*)c->dctx, c->lse, (float*)c->dqkv, c->B, c->T, c->H, D,
+                          s, mfma);
+}
+
 size_t f32_carve(const vl_model* m, Workspace& w, int train, char* base, size_t off0) {
     const int D = m->D, L = m->L, MLP = m->MLP;
     const int64_t Mpad = w.Mpad, Mppad = w.Mppad;

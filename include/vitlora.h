@@ -373,6 +373,64 @@ typedef struct vl_gemm_case {
 /* The patch-gradient epilogues flag a non-finite gradient in the handle's error word: vl_check_errors reports it. */
 int vl_debug_gemm(vl_model* m, const vl_gemm_case* c, void* stream);
 
+/* One ATTENTION kernel on CALLER-OWNED device buffers, named explicitly (tests/test_hip_attn_ref.py compares every output element
+ * with a float64 softmax attention and its textbook backward; the model-level tests only see these kernels through several layers).
+ * `kernel` picks the kernel itself, not a route: no process-wide switch (attn_ring, VITLORA_ATTN_RING, VITLORA_F32_ATTN,
+ * VITLORA_ATTN_IMG) is read.  The template instantiation follows T as in the product: <1> for T <= 32, else <7>.
+ * Head dimension 64, D = 64 H, softmax scale 1/8.  Layouts (16-bit elements of the handle's type; fp32 on an fp32 handle):
+ *   qkv, dqkv [B*T][3D]  (q | k | v column groups of D, head hd at columns 64 hd .. 64 hd + 63 of its group)
+ *   ctx, dctx [B*T][D]   (CLS kernels: compact [B][D], the row of token 0)
+ *   lse       [B][H][T] fp32  (CLS kernels: [B][H]).  UNIT: the 16-bit kernels keep the BASE-2 log-sum-exp of the scaled scores,
+ *             lse2 = log2(sum_k exp(q.k / 8)); the fp32 kernels keep the NATURAL log-sum-exp.
+ *   down_W    forward: Ad [>= r rows][D]; backward: Bd [3r rows][3D], rows 0 / r / 2r .. = the query / key / value adapter, each
+ *             read at its own column group (rows of a module that `mods` leaves out are not read)
+ *   down_out  t / u [B*T][64]
+ * What each kernel writes (rows = tokens 0 .. B*T - 1; nothing outside these is touched, padding rows included):
+ *   VL_ATTN_FWD, VL_ATTN_IMG_FWD, VL_ATTN_F32_*_FWD   every element of ctx and of lse.
+ *   VL_ATTN_IMG_FWD with down_W                        additionally t = ctx Ad^T summed over heads in fp32 from the 16-bit ctx: ALL 64
+ *                                                      columns of every row are written -- the rows are zeroed first, then columns
+ *                                                      0 .. r - 1 (r <= 4) or 0 .. 7 (r > 4) receive the sums; columns >= r end as zero.
+ *   VL_ATTN_BWD, VL_ATTN_IMG_BWD, VL_ATTN_RING_BWD,    every element of dqkv (dq | dk | dv).
+ *   VL_ATTN_F32_*_BWD
+ *   VL_ATTN_IMG_BWD / VL_ATTN_RING_BWD with down_W     additionally u = dqkv Bd^T: all 64 columns of every row are zeroed, then the
+ *                                                      module md (0 q, 1 k, 2 v) of every bit set in `mods` receives its r sums at
+ *                                                      columns md r .. md r + r - 1; the column groups of the other modules stay zero.
+ *   VL_ATTN_CLS_FWD                                    ctx row and lse of token 0 only (compact buffers).
+ *   VL_ATTN_CLS_BWD                                    every element of dqkv: dk, dv of every token, dq of token 0, and ZEROS in
+ *                                                      the dq columns of every other token.
+ * The backward kernels read ctx only for delta = rowsum(dctx * ctx).
+ * VALIDATES AND REFUSES, nothing is launched then: VL_ERR_ARG for a null required pointer (qkv always; ctx, lse; dctx and dqkv for a
+ * backward kernel; down_out with down_W), a pointer that is not 16-byte aligned, T < 2, B < 1, H < 1, an unknown `kernel` or one of
+ * the other precision, r outside 1 .. 8 or mods outside 1 .. 7 when down_W is given; VL_ERR_UNSUPPORTED for T above the kernel's
+ * limit (224; CLS kernels 256; ring kernel 200) and for down_W on a kernel without a fused down projection.
+ * Only enqueues ONE kernel on `stream`: no allocation, no synchronisation, the handle's workspace is not touched. */
+#define VL_ATTN_FWD 0             /* attn_fwd32_kernel: one workgroup per (image, head) */
+#define VL_ATTN_BWD 1             /* attn_bwd32_kernel */
+#define VL_ATTN_IMG_FWD 2         /* attn_fwd_img_kernel: one workgroup per image, optional t */
+#define VL_ATTN_IMG_BWD 3         /* attn_bwd_img_kernel: two-phase per-image backward, optional u */
+#define VL_ATTN_RING_BWD 4        /* attn_bwd_ring_kernel: single-pass per-image backward, optional u, T <= 200 */
+#define VL_ATTN_CLS_FWD 5         /* attn_cls_fwd_kernel */
+#define VL_ATTN_CLS_BWD 6         /* attn_cls_bwd_kernel */
+#define VL_ATTN_F32_MFMA_FWD 7    /* fp32 handle: attn_fwd_f32_mfma_kernel */
+#define VL_ATTN_F32_MFMA_BWD 8    /* attn_bwd_f32_mfma_kernel */
+#define VL_ATTN_F32_SCALAR_FWD 9  /* attn_fwd_f32_kernel */
+#define VL_ATTN_F32_SCALAR_BWD 10 /* attn_bwd_f32_kernel */
+typedef struct vl_attn_case {
+    int32_t B, T, H;      /* images, tokens per image, heads (D = 64 H) */
+    int32_t kernel;       /* VL_ATTN_* */
+    const void* qkv;
+    void* ctx;            /* written by a forward kernel, read by a backward kernel */
+    float* lse;           /* likewise */
+    const void* dctx;     /* backward kernels */
+    void* dqkv;           /* backward kernels */
+    const void* down_W;   /* NULL: no down projection */
+    void* down_out;
+    int32_t r;            /* LoRA rank of the down projection, 1 .. 8 */
+    uint32_t mods;        /* backward: bit 0 / 1 / 2 = query / key / value adapted (forward: ignored) */
+    int32_t reserved[4];
+} vl_attn_case;
+int vl_debug_attention(vl_model* m, const vl_attn_case* c, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
