@@ -14,10 +14,11 @@ Everything numeric runs in libvitlora_hip.so (include/vitlora.h); there is no CP
 """
 from ._lib import LIB_PATH, NonFiniteGradient, VitLoraError, check  # noqa: F401
 from .engine import (IMAGENET_MEAN, IMAGENET_STD, ArchConfig, Engine, LoraSpec,  # noqa: F401
-                     canonical_key, expected_keys, resolve_targets)
+                     apgd_schedule, canonical_key, expected_keys, resolve_targets)
 
+# APGD, AutoAttack (auto_attack.py:98-108) and the other facade names resolve lazily from .attacks / .model / ... below
 __all__ = ["ArchConfig", "Engine", "LoraSpec", "VitLoraError", "NonFiniteGradient", "LIB_PATH", "IMAGENET_MEAN", "IMAGENET_STD",
-           "resolve_targets", "canonical_key", "expected_keys"]
+           "resolve_targets", "canonical_key", "expected_keys", "apgd_schedule", "APGD", "AutoAttack"]
 
 
 def __getattr__(name):

@@ -118,6 +118,38 @@ ATTN_KERNELS = {"fwd": 0, "bwd": 1, "img_fwd": 2, "img_bwd": 3, "ring_bwd": 4, "
 SIGNATURES["vl_debug_attention"] = (C.c_int, [C.c_void_p, C.POINTER(VLAttnCase), C.c_void_p])
 
 
+class VLApgdArgs(C.Structure):
+    """vl_apgd_args of include/vitlora.h (field for field)."""
+    _fields_ = [
+        ("x0", C.c_void_p), ("labels", C.c_void_p), ("batch", C.c_int32), ("steps", C.c_int32),
+        ("eps", C.c_float), ("rho", C.c_float), ("x_init", C.c_void_p),
+        ("random_start", C.c_int32), ("reserved0", C.c_int32), ("seed", C.c_uint64),
+        ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t),
+        ("x_best", C.c_void_p), ("x_best_adv", C.c_void_p), ("loss_best", C.c_void_p), ("robust", C.c_void_p),
+        ("trace_loss", C.c_void_p), ("trace_step", C.c_void_p), ("trace_pred", C.c_void_p),
+        ("stream", C.c_void_p), ("reserved", C.c_int32 * 4),
+    ]
+
+
+class VLApgdTrackCase(C.Structure):
+    """vl_apgd_track_case of include/vitlora.h (field for field)."""
+    _fields_ = [
+        ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t),
+        ("batch", C.c_int32), ("steps", C.c_int32), ("reset", C.c_int32), ("reserved0", C.c_int32),
+        ("eps", C.c_float), ("rho", C.c_float),
+        ("loss_img", C.c_void_p), ("logits", C.c_void_p), ("labels", C.c_void_p),
+        ("step_out", C.c_void_p), ("flags_out", C.c_void_p), ("loss_best_out", C.c_void_p), ("robust_out", C.c_void_p),
+    ]
+
+
+SIGNATURES.update({
+    "vl_apgd_scratch_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "vl_apgd_attack": (C.c_int, [C.c_void_p, C.POINTER(VLApgdArgs)]),
+    "vl_apgd_step": (C.c_int, [C.c_void_p] * 9 + [C.c_int, C.c_int64, C.c_float, C.c_float, C.c_int, C.c_void_p]),
+    "vl_debug_apgd_track": (C.c_int, [C.c_void_p, C.POINTER(VLApgdTrackCase), C.c_void_p]),
+})
+
+
 class VLSwinConfig(C.Structure):
     _fields_ = [("image_size", C.c_int32), ("patch_size", C.c_int32), ("embed_dim", C.c_int32), ("depths", C.c_int32 * 4),
                 ("heads", C.c_int32 * 4), ("window", C.c_int32), ("num_labels", C.c_int32), ("ln_eps", C.c_float),

@@ -126,4 +126,92 @@ class PGD(_Attack):
         return self._finish(eng, adv)
 
 
-__all__ = ["batched_fgsm_attack", "FGSM", "PGD", "LogitsModel"]
+def _apgd_ce(eng, x, labels, eps, steps, rho, n_restarts, seed, random_start=True):
+    """APGD-CE with restarts on [0,1] images (the engine's normalisation is the caller's to set): starts from `x`, and an image
+    that is classified correctly before the attack takes the misclassified point of the first restart that fools it.  Returns
+    (adv, still_robust [B] bool, clean_correct [B] bool, result of the last restart)."""
+    labels = labels.to(device=eng.device, dtype=torch.int64)
+    correct = eng.forward(x, normalise=True).argmax(1) == labels
+    robust = correct.clone()
+    adv = x.clone()
+    res = None
+    for r in range(max(1, int(n_restarts))):
+        res = eng.apgd_attack(x, labels, eps, steps, rho=rho, random_start=random_start, seed=int(seed) + r)
+        take = robust & ~res["robust"]
+        adv = torch.where(take.view(-1, 1, 1, 1), res["x_best_adv"], adv)
+        robust = robust & res["robust"]
+    return adv, robust, correct, res
+
+
+class APGD(_Attack):
+    """torchattacks.APGD(model, norm='Linf', eps, steps, n_restarts, seed, loss='ce', rho): Auto-PGD on cross-entropy, the
+    whole loop on the device (vl_apgd_attack).  Restart r uses the library's counter-based random start with seed + r.
+    The algorithm is the library's restatement of the autoattack package (include/vitlora.h): parity with the package is
+    unpinned.  After a call `last` holds the last restart's x_best / x_best_adv / loss_best / robust."""
+
+    def __init__(self, model, norm="Linf", eps=8 / 255, steps=10, n_restarts=1, seed=0, loss="ce", rho=0.75):
+        super().__init__(model)
+        if norm != "Linf":
+            raise ValueError(f"APGD: only norm='Linf' is built (got {norm!r})")
+        if loss != "ce":
+            raise ValueError(f"APGD: only loss='ce' is built (got {loss!r})")
+        self.norm, self.eps, self.steps, self.n_restarts, self.seed, self.loss, self.rho = norm, eps, steps, n_restarts, seed, loss, rho
+        self.last = None
+
+    def forward(self, images, labels):
+        vit, eng, x = self._prepare(images)
+        if self._norm is None:
+            eng.set_normalization([0.0, 0.0, 0.0], [1.0, 1.0, 1.0])
+        adv, _, _, self.last = _apgd_ce(eng, x, labels, self.eps, self.steps, self.rho, self.n_restarts, self.seed)
+        if self._norm is None:
+            from .engine import IMAGENET_MEAN, IMAGENET_STD
+            eng.set_normalization(IMAGENET_MEAN, IMAGENET_STD)   # back to the library default
+        return self._finish(eng, adv)
+
+
+class AutoAttack:
+    """autoattack.AutoAttack(model, norm='Linf', eps, version, attacks_to_run, seed) as auto_attack.py:98-108 uses it.
+    Only the first component of the standard suite, APGD-CE, is built: version='custom' with attacks_to_run=['apgd-ce'] runs
+    it; version='standard' raises NotImplementedError.  Images are in [0,1]; the model is fed (x - mean) / std (the reference
+    wraps its model in a NormalizedModel, auto_attack.py:47-55), ImageNet constants unless `mean` / `std` are given."""
+
+    MISSING = ("apgd-t", "fab-t", "square")
+
+    def __init__(self, model, norm="Linf", eps=0.3, version="standard", attacks_to_run=(), seed=None, device=None, verbose=False,
+                 steps=100, n_restarts=1, rho=0.75, mean=None, std=None):
+        if norm != "Linf":
+            raise ValueError(f"AutoAttack: only norm='Linf' is built (got {norm!r})")
+        if version == "standard":
+            raise NotImplementedError("AutoAttack(version='standard') needs APGD-T, FAB-T and Square, which are not built; "
+                                      "use version='custom', attacks_to_run=['apgd-ce']")
+        if version != "custom":
+            raise ValueError(f"AutoAttack: version must be 'standard' or 'custom' (got {version!r})")
+        bad = [a for a in attacks_to_run if a != "apgd-ce"]
+        if bad or not list(attacks_to_run):
+            raise NotImplementedError(f"AutoAttack: attacks_to_run must be ['apgd-ce'] (not built: {bad})")
+        self.model, self.norm, self.eps, self.version, self.attacks_to_run = model, norm, eps, version, list(attacks_to_run)
+        self.seed = 0 if seed is None else int(seed)
+        self.steps, self.n_restarts, self.rho = steps, n_restarts, rho
+        from .engine import IMAGENET_MEAN, IMAGENET_STD
+        self.mean = [float(v) for v in (mean if mean is not None else IMAGENET_MEAN)]
+        self.std = [float(v) for v in (std if std is not None else IMAGENET_STD)]
+        self.robust_accuracy = None
+
+    def run_standard_evaluation(self, x_orig, y_orig, bs=250):
+        vit = _unwrap(self.model)
+        eng = vit._engine()
+        vit.sync_params()
+        eng.set_normalization(self.mean, self.std)
+        x_all = x_orig.detach().to(device=eng.device, dtype=torch.float32).contiguous()
+        y_all = y_orig.to(device=eng.device, dtype=torch.int64)
+        out, n_robust = [], 0
+        for lo in range(0, x_all.shape[0], int(bs)):
+            x, y = x_all[lo:lo + bs], y_all[lo:lo + bs]
+            adv, robust, _, _ = _apgd_ce(eng, x, y, self.eps, self.steps, self.rho, self.n_restarts, self.seed)
+            out.append(adv)
+            n_robust += int(robust.sum().item())
+        self.robust_accuracy = n_robust / max(1, x_all.shape[0])
+        return torch.cat(out)
+
+
+__all__ = ["batched_fgsm_attack", "FGSM", "PGD", "APGD", "AutoAttack", "LogitsModel"]

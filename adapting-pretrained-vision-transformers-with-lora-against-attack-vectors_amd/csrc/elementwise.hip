@@ -2,6 +2,8 @@
 // head with cross-entropy, the fused FGSM/PGD update (K10), the PGD random start (K11),
 // flat Adam (K12), the save_images quantiser and the weight packers.
 // Every kernel moves 16 bytes per lane wherever the layout allows it.
+#include <algorithm>
+
 #include "kernels.h"
 #include "prof.h"
 
@@ -777,6 +779,200 @@ __global__ void pgd_init_kernel(float* __restrict__ adv, const float* __restrict
     }
 }
 
+// ---------------------------------------------------------------------------------
+// Auto-PGD (APGD-CE, L-inf; Croce & Hein 2020).  The algorithm is the restatement in DESIGN.md section 3.9 -- written from
+// memory of the autoattack package's autopgd_base.py, which is not installed here: parity with the package is UNPINNED.
+// One captured iteration (forward, CE, backward, apgd_track_kernel, apgd_step_kernel) serves every iteration index: what
+// differs between iterations (momentum, checkpoint, first / last) is read from a schedule table at a device-side counter.
+// The counter is two words: the track kernel reads ctr[0] and writes ctr[1] = ctr[0] + 1, the step kernel reads ctr[1] and
+// writes ctr[0] = ctr[1] -- no kernel reads a word that one of its own blocks writes.
+// ---------------------------------------------------------------------------------
+// Schedule table entry j (replay j evaluates the point of iteration j - 1 and makes the point of iteration j) and the counter.
+__global__ void apgd_sched_kernel(ApgdSched* __restrict__ sched, int32_t* __restrict__ ctr, int N, int k0, int kmin, int dec) {
+    if (blockIdx.x || threadIdx.x) return;
+    int k = k0, cnt = 0;
+    sched[0] = {1.f, 0, APGD_FIRST | (N == 0 ? APGD_LAST : 0), 0};
+    for (int i = 0; i < N; ++i) {               // iteration i is evaluated by replay i + 1
+        ApgdSched e = {0.75f, 0, i + 1 == N ? APGD_LAST : 0, 0};     // a of iteration i + 1 (iteration 0 alone has a = 1)
+        if (++cnt == k) { e.k = k; k = k - dec > kmin ? k - dec : kmin; cnt = 0; }
+        sched[i + 1] = e;
+    }
+    ctr[0] = 0; ctr[1] = 0; ctr[2] = 0; ctr[3] = 0;
+}
+
+// start = x0 + eps * t / max|t|, t ~ U(-1, 1) from the counter-based generator, the maximum taken per image; one block per image
+__global__ __launch_bounds__(256) void apgd_rand_init_kernel(float* __restrict__ x_adv, const float* __restrict__ x0, float eps,
+                                                              uint64_t seed, int64_t n) {
+    __shared__ float red[4];
+    const int64_t base = (int64_t)blockIdx.x * n;
+    auto draw = [&](int64_t i) -> float {
+        const uint64_t r = mix64(seed * 0xD1342543DE82EF95ull + (uint64_t)(base + i));
+        return 2.f * ((float)(r >> 40) * (1.0f / 16777216.0f)) - 1.f;
+    };
+    float mx = 0.f;
+    for (int64_t i = threadIdx.x; i < n; i += 256) mx = fmaxf(mx, fabsf(draw(i)));
+    mx = wave_max(mx);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    mx = mx > 0.f ? mx : 1.f;
+    for (int64_t i = threadIdx.x; i < n; i += 256) {
+        const float v = x0[base + i] + (eps * draw(i)) / mx;
+        x_adv[base + i] = fminf(fmaxf(v, 0.f), 1.f);
+    }
+}
+
+// x_adv = clamp(start, 0, 1) for a start point the caller gives (x0 itself or x_init)
+__global__ void apgd_start_kernel(float* __restrict__ x_adv, const float* __restrict__ src, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride) x_adv[i] = fminf(fmaxf(src[i], 0.f), 1.f);
+}
+
+// Steps 2-4 of one iteration for one image per wave (four per block): prediction from the logits row, best-loss and robust
+// bookkeeping, the checkpoint test, the new step size; writes the flag word the step kernel acts on and the trace rows.
+__global__ __launch_bounds__(256) void apgd_track_kernel(ApgdState st, const float* __restrict__ loss_img,
+                                                         const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                         int B, int C, int N, float eps, float rho) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int j = st.ctr[0];
+    if (blockIdx.x == 0 && threadIdx.x == 0) st.ctr[1] = j + 1;
+    if (b >= B || (unsigned)j > (unsigned)N) return;     // a replay past the table does nothing
+    const ApgdSched e = st.sched[j];
+    // pred = (argmax == y), the first maximum as torch.argmax
+    const float* lr = logits + (int64_t)b * C;
+    float mx = -INFINITY;
+    int am = 0x7fffffff;
+    for (int c = lane; c < C; c += 64) { const float v = lr[c]; if (v > mx) { mx = v; am = c; } }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(mx, o, 64);
+        const int oa = __shfl_xor(am, o, 64);
+        if (ov > mx || (ov == mx && oa < am)) { mx = ov; am = oa; }
+    }
+    const int pred = ((int64_t)am == labels[b]) ? 1 : 0;
+    const float loss = loss_img[b];
+    float step, lb, lbl;
+    int red_last, rob;
+    uint32_t fl = 0;
+    if (e.flags & APGD_FIRST) {        // the start point: x_best = x_best_adv = x_adv, grad_best = grad
+        step = 2.f * eps; lb = loss; lbl = loss; red_last = 1; rob = pred;
+        fl = APGD_IMPROVED | APGD_FOOLED;
+    } else {
+        step = st.step[b]; lb = st.loss_best[b]; lbl = st.loss_best_last[b]; red_last = st.reduced_last[b];
+        rob = st.robust[b] & pred;
+        if (!pred) fl |= APGD_FOOLED;
+        if (loss > lb) { lb = loss; fl |= APGD_IMPROVED; }
+        if (e.k > 0) {                 // checkpoint: loss_steps[i] is trace row i + 1, row "-1" reads 0
+            const int i = j - 1;
+            int t = 0;
+            for (int c = lane; c < e.k; c += 64) {
+                const int hi = i - c, lo = hi - 1;
+                const float vh = hi == i ? loss : (hi < 0 ? 0.f : st.tr_loss[(int64_t)(hi + 1) * B + b]);
+                const float vl = lo < 0 ? 0.f : st.tr_loss[(int64_t)(lo + 1) * B + b];
+                t += vh > vl ? 1 : 0;
+            }
+            t = (int)wave_sum((float)t);
+            const bool osc = (float)t <= (float)e.k * rho;
+            const bool noimp = !red_last && lbl >= lb;
+            const bool red = osc || noimp;
+            red_last = red ? 1 : 0;
+            lbl = lb;
+            if (red) { step = step * 0.5f; fl |= APGD_RESTART; }
+        }
+    }
+    if (lane == 0) {
+        st.step[b] = step; st.loss_best[b] = lb; st.loss_best_last[b] = lbl; st.reduced_last[b] = red_last;
+        st.robust[b] = rob; st.flags[b] = fl;
+        st.tr_loss[(int64_t)j * B + b] = loss;
+        st.tr_pred[(int64_t)j * B + b] = pred;
+        if (j < N) st.tr_step[(int64_t)j * B + b] = step;      // the step size iteration j's update uses
+    }
+}
+
+// P(v) = clamp(min(max(v, x0 - eps), x0 + eps), 0, 1); z = P(xa + step sign(g)); new = P((xa + (z - xa) a) + g2 (1 - a)),
+// every operation rounded on its own (no FMA contraction: the reference restatement is bit-exact)
+__device__ __forceinline__ float apgd_update(float xa, float xo, float x0, float g, float step, float eps, float a, float oma) {
+#pragma clang fp contract(off)
+    const float lo = x0 - eps, hi = x0 + eps;
+    const float g2 = xa - xo;
+    const float v = xa + step * sgn(g);
+    const float z = fminf(fmaxf(fminf(fmaxf(v, lo), hi), 0.f), 1.f);
+    const float d = (z - xa) * a;
+    const float m = g2 * oma;
+    const float w = (xa + d) + m;
+    return fminf(fmaxf(fminf(fmaxf(w, lo), hi), 0.f), 1.f);
+}
+
+// The elementwise pass of one iteration: blockIdx.y = image, so the flag branches are uniform over the block.  In ONE read of
+// x_adv, x_old, x0 and grad: the copies the track kernel asked for (improved: x_best, grad_best <- x_adv, grad; fooled:
+// x_best_adv <- x_adv; restart: x_adv, grad <- x_best, grad_best -- after the improved copy, so both together leave x_adv as it
+// is), then step 1 of the NEXT iteration (x_old <- x_adv, x_adv <- new point) unless this is the last evaluation.  24 B per
+// element (four 16-byte non-temporal loads, two stores; pgd_step_kernel's access shape) plus the copies where a flag is set.
+// sched != nullptr: a / last come from the table entry at ctr[1] - 1; nullptr: from the arguments (vl_apgd_step).
+__global__ __launch_bounds__(256) void apgd_step_kernel(float* __restrict__ x_adv, float* __restrict__ x_old,
+                                                        float* __restrict__ x_best, float* __restrict__ x_best_adv,
+                                                        float* __restrict__ grad_best, const float* __restrict__ x0,
+                                                        const float* __restrict__ grad, const uint32_t* __restrict__ flags,
+                                                        const float* __restrict__ step, int64_t n4, float eps,
+                                                        const ApgdSched* __restrict__ sched, int32_t* __restrict__ ctr, int N,
+                                                        float a, int last, int* __restrict__ err) {
+#pragma clang fp contract(off)
+    if (sched) {
+        const int j = ctr[1] - 1;
+        if ((unsigned)j > (unsigned)N) return;
+        a = sched[j].a;
+        last = sched[j].flags & APGD_LAST;
+        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) ctr[0] = j + 1;
+    }
+    const int b = blockIdx.y;
+    const uint32_t fl = flags[b];
+    const float st = step[b];
+    const float oma = 1.f - a;
+    const bool improved = fl & APGD_IMPROVED, fooled = fl & APGD_FOOLED, restart = (fl & APGD_RESTART) && !improved;
+    if (last && !improved && !fooled) return;        // nothing to copy, no further point to make
+    const int64_t base = (int64_t)b * n4;
+    f32x4* const pa = (f32x4*)x_adv + base;
+    f32x4* const po = (f32x4*)x_old + base;
+    f32x4* const pb = (f32x4*)x_best + base;
+    f32x4* const pf = (f32x4*)x_best_adv + base;
+    f32x4* const pg = (f32x4*)grad_best + base;
+    const f32x4* const p0 = (const f32x4*)x0 + base;
+    const f32x4* const pgr = (const f32x4*)grad + base;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += 2 * stride) {
+        const int64_t k = i + stride;
+        const bool two = k < n4;
+        f32x4 a0 = __builtin_nontemporal_load(pa + i);
+        const f32x4 o0 = __builtin_nontemporal_load(po + i);
+        const f32x4 x0v = __builtin_nontemporal_load(p0 + i);
+        f32x4 g0 = __builtin_nontemporal_load(pgr + i);
+        f32x4 a1 = a0, o1 = o0, x1v = x0v, g1 = g0;
+        if (two) {
+            a1 = __builtin_nontemporal_load(pa + k);
+            o1 = __builtin_nontemporal_load(po + k);
+            x1v = __builtin_nontemporal_load(p0 + k);
+            g1 = __builtin_nontemporal_load(pgr + k);
+        }
+        bool bad = false;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) bad |= !(fabsf(g0[q]) < INFINITY) | !(fabsf(g1[q]) < INFINITY);
+        if (err && bad) *err = 2;
+        if (improved) { pb[i] = a0; pg[i] = g0; if (two) { pb[k] = a1; pg[k] = g1; } }
+        if (fooled) { pf[i] = a0; if (two) pf[k] = a1; }
+        if (last) continue;
+        if (restart) { a0 = pb[i]; g0 = pg[i]; if (two) { a1 = pb[k]; g1 = pg[k]; } }
+        f32x4 n0, n1;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            n0[q] = apgd_update(a0[q], o0[q], x0v[q], g0[q], st, eps, a, oma);
+            n1[q] = apgd_update(a1[q], o1[q], x1v[q], g1[q], st, eps, a, oma);
+        }
+        po[i] = a0; pa[i] = n0;
+        if (two) { po[k] = a1; pa[k] = n1; }
+    }
+}
+
 __global__ void fill_random_h16_kernel(h16* __restrict__ dst, size_t n, uint64_t seed) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -1095,6 +1291,36 @@ void k_zero(void* p, size_t bytes, hipStream_t s) {
 void k_pgd_init(float* adv, const float* x0, float eps, float lo, float hi, uint64_t seed, int64_t n, hipStream_t s) {
     ProfScope prof_("pgd_init_kernel", 0.0, (double)n * 8.0, s);
     hipLaunchKernelGGL(pgd_init_kernel, dim3(nblk(n, 256, 4096)), dim3(256), 0, s, adv, x0, eps, lo, hi, seed, n);
+}
+void apgd_schedule_constants(int N, int* k0, int* kmin, int* dec) {
+    *k0 = std::max((int)(0.22 * N), 1); *kmin = std::max((int)(0.06 * N), 1); *dec = std::max((int)(0.03 * N), 1);
+}
+void k_apgd_sched(ApgdSched* sched, int32_t* ctr, int N, hipStream_t s) {
+    int k0, kmin, dec;
+    apgd_schedule_constants(N, &k0, &kmin, &dec);
+    hipLaunchKernelGGL(apgd_sched_kernel, dim3(1), dim3(64), 0, s, sched, ctr, N, k0, kmin, dec);
+}
+void k_apgd_rand_init(float* x_adv, const float* x0, float eps, uint64_t seed, int B, int64_t n_img, hipStream_t s) {
+    ProfScope prof_("apgd_rand_init_kernel", 0.0, (double)B * n_img * 8.0, s);
+    hipLaunchKernelGGL(apgd_rand_init_kernel, dim3(B), dim3(256), 0, s, x_adv, x0, eps, seed, n_img);
+}
+void k_apgd_start(float* x_adv, const float* src, int64_t n, hipStream_t s) {
+    ProfScope prof_("apgd_start_kernel", 0.0, (double)n * 8.0, s);
+    hipLaunchKernelGGL(apgd_start_kernel, dim3(nblk(n, 256, 4096)), dim3(256), 0, s, x_adv, src, n);
+}
+void k_apgd_track(const ApgdState& st, const float* loss_img, const float* logits, const int64_t* labels, int B, int C, int N,
+                  float eps, float rho, hipStream_t s) {
+    ProfScope prof_("apgd_track_kernel", 0.0, (double)B * (C + 16) * 4.0, s);
+    hipLaunchKernelGGL(apgd_track_kernel, dim3((B + 3) / 4), dim3(256), 0, s, st, loss_img, logits, labels, B, C, N, eps, rho);
+}
+void k_apgd_step(float* x_adv, float* x_old, float* x_best, float* x_best_adv, float* grad_best, const float* x0,
+                 const float* grad, const uint32_t* flags, const float* step, int B, int64_t n_img, float eps,
+                 const ApgdSched* sched, int32_t* ctr, int N, float a, int last, hipStream_t s, int* err) {
+    ProfScope prof_("apgd_step_kernel", 0.0, (double)B * n_img * 24.0, s);
+    const int64_t n4 = n_img / 4;                    // n_img % 4 == 0 is the caller's to check
+    const int per_img = nblk((n4 + 1) / 2, 256, std::max(1, 8192 / B));
+    hipLaunchKernelGGL(apgd_step_kernel, dim3(per_img, B), dim3(256), 0, s, x_adv, x_old, x_best, x_best_adv, grad_best, x0, grad,
+                       flags, step, n4, eps, sched, ctr, N, a, last, err);
 }
 void k_adam(float* p, const float* g, float* m, float* v, float lr, float b1, float b2, float eps, int t, int64_t n,
             hipStream_t s, int* err) {

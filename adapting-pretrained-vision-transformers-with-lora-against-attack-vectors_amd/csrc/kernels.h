@@ -48,6 +48,36 @@ void k_pgd_step(float* adv, const float* x0, const float* grad, float eps, float
                 hipStream_t s, int* err = nullptr);
 void k_zero(void* p, size_t bytes, hipStream_t s);   // bytes % 16 == 0; a kernel node, not a memset node, under capture
 void k_pgd_init(float* adv, const float* x0, float eps, float lo, float hi, uint64_t seed, int64_t n, hipStream_t s);
+// ---- Auto-PGD (APGD-CE, L-inf): elementwise.hip ----
+// Schedule entry j: replay j of the captured iteration evaluates the point of iteration j - 1 and makes the point of iteration j.
+struct ApgdSched {
+    float a;            // momentum of iteration j's update (1 at j = 0, else .75)
+    int32_t k;          // > 0: iteration j - 1 ends a checkpoint window of k iterations
+    int32_t flags;      // APGD_FIRST: the evaluation of the start point; APGD_LAST: no further point is made
+    int32_t pad;
+};
+enum { APGD_FIRST = 1, APGD_LAST = 2 };
+enum { APGD_IMPROVED = 1u, APGD_FOOLED = 2u, APGD_RESTART = 4u };     // per-image flag word of one iteration
+struct ApgdState {      // per-image scalars, the schedule and the trace rows, all inside the caller's scratch
+    int32_t* ctr;       // [4]: ctr[0] read by the track kernel, ctr[1] by the step kernel
+    ApgdSched* sched;   // [N + 1]
+    float *step, *loss_best, *loss_best_last;     // [B]
+    int32_t *reduced_last, *robust;               // [B]
+    uint32_t* flags;                              // [B]
+    float* tr_loss;     // [N + 1][B]: row j = loss at replay j (row 0 the start point; loss_steps[i] = row i + 1)
+    float* tr_step;     // [N][B]: the step size iteration j's update used
+    int32_t* tr_pred;   // [N + 1][B]
+};
+void apgd_schedule_constants(int N, int* k0, int* kmin, int* dec);
+void k_apgd_sched(ApgdSched* sched, int32_t* ctr, int N, hipStream_t s);     // fills the table, zeroes the counter
+void k_apgd_rand_init(float* x_adv, const float* x0, float eps, uint64_t seed, int B, int64_t n_img, hipStream_t s);
+void k_apgd_start(float* x_adv, const float* src, int64_t n, hipStream_t s);     // x_adv = clamp(src, 0, 1)
+void k_apgd_track(const ApgdState& st, const float* loss_img, const float* logits, const int64_t* labels, int B, int C, int N,
+                  float eps, float rho, hipStream_t s);
+// sched != nullptr: a / last are read from sched[ctr[1] - 1] and ctr[0] is advanced; nullptr: the arguments.  n_img % 4 == 0.
+void k_apgd_step(float* x_adv, float* x_old, float* x_best, float* x_best_adv, float* grad_best, const float* x0,
+                 const float* grad, const uint32_t* flags, const float* step, int B, int64_t n_img, float eps,
+                 const ApgdSched* sched, int32_t* ctr, int N, float a, int last, hipStream_t s, int* err = nullptr);
 // err (optional): set to 3 when a gradient element is not finite (that element is skipped)
 void k_adam(float* p, const float* g, float* m, float* v, float lr, float b1, float b2, float eps, int t, int64_t n,
             hipStream_t s, int* err = nullptr);

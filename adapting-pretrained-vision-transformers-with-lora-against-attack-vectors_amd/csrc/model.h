@@ -99,6 +99,11 @@ struct GraphEntry {
     hipGraphExec_t exec;
     int chains;
     hipGraphExec_t exec1;     // chains == 2: the second half-batch's iteration (launched on the side stream)
+    // kind 1 = the APGD iteration (vl_apgd_attack): its kernels read the caller's scratch, so the key also holds that pointer,
+    // the schedule length and rho (alpha is unused)
+    int kind = 0, steps = 0;
+    const void* scratch = nullptr;
+    float rho = 0.f;
 };
 
 }  // namespace VLNS

@@ -668,6 +668,17 @@ static void drop_graphs(vl_model* m) {
     m->graphs.clear();
 }
 
+// the cache holds the 8 most recent captured iterations (PGD and APGD alike)
+static void remember_graph(vl_model* m, const GraphEntry& e) {
+    if (m->graphs.size() >= 8) {
+        (void)hipGraphExecDestroy(m->graphs.front().exec);
+        if (m->graphs.front().exec1) (void)hipGraphExecDestroy(m->graphs.front().exec1);
+        m->graphs.erase(m->graphs.begin());
+    }
+    m->graphs.push_back(e);
+    m->n_captures++;
+}
+
 static int chain_resources(vl_model* m) {
     if (!m->side_stream) HIPCHK(hipStreamCreateWithFlags(&m->side_stream, hipStreamNonBlocking));
     if (!m->ev_fork) HIPCHK(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
@@ -1198,7 +1209,7 @@ int vl_pgd_attack(vl_model* m, const float* x0, const int64_t* labels, int batch
         } else {
             hipGraphExec_t exec = nullptr, exec1 = nullptr;
             for (GraphEntry& g : m->graphs)
-                if (g.B == batch && g.eps == eps && g.alpha == alpha && g.chains == chains) { exec = g.exec; exec1 = g.exec1; break; }
+                if (g.kind == 0 && g.B == batch && g.eps == eps && g.alpha == alpha && g.chains == chains) { exec = g.exec; exec1 = g.exec1; break; }
             if (!exec) {
                 // Captured cold: nothing has to run eagerly first.  (Round 2 ran the first iteration eagerly because replays of
                 // a graph captured in a fresh process differed from the eager result.  Cause, established in round 3 with
@@ -1227,13 +1238,7 @@ int vl_pgd_attack(vl_model* m, const float* x0, const int64_t* labels, int batch
                 };
                 if ((rc = capture(0, &exec))) return rc;
                 if (chains == 2 && (rc = capture(1, &exec1))) { (void)hipGraphExecDestroy(exec); return rc; }
-                if (m->graphs.size() >= 8) {
-                    (void)hipGraphExecDestroy(m->graphs.front().exec);
-                    if (m->graphs.front().exec1) (void)hipGraphExecDestroy(m->graphs.front().exec1);
-                    m->graphs.erase(m->graphs.begin());
-                }
-                m->graphs.push_back({batch, eps, alpha, exec, chains, exec1});
-                m->n_captures++;
+                remember_graph(m, {batch, eps, alpha, exec, chains, exec1});
             }
             if (chains == 2) {
                 HIPCHK(hipEventRecord(m->ev_fork, s));
@@ -1254,6 +1259,159 @@ int vl_pgd_attack(vl_model* m, const float* x0, const int64_t* labels, int batch
     HIPCHK(hipMemcpyAsync(adv_out, w.stage_adv, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     return VL_OK;
 }
+
+// ---- Auto-PGD (APGD-CE, L-inf; include/vitlora.h) --------------------------
+// Everything the attack keeps between iterations, carved from the caller's scratch (base == nullptr: size only).
+struct ApgdLayout {
+    float *x0, *x_adv, *x_old, *x_best, *x_best_adv, *grad_best;
+    int64_t* labels;
+    ApgdState st;
+};
+static size_t apgd_carve(const vl_model* m, int B, int N, char* base, ApgdLayout& L) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) -> char* {
+        char* p = base ? base + off : nullptr;
+        off += (size_t)round_up((int64_t)bytes, 256);
+        return p;
+    };
+    const size_t img = (size_t)B * 3 * m->S * m->S * 4, row = (size_t)B * 4;
+    L.x0 = (float*)take(img); L.x_adv = (float*)take(img); L.x_old = (float*)take(img);
+    L.x_best = (float*)take(img); L.x_best_adv = (float*)take(img); L.grad_best = (float*)take(img);
+    L.labels = (int64_t*)take((size_t)B * 8);
+    L.st.ctr = (int32_t*)take(16);
+    L.st.sched = (ApgdSched*)take((size_t)(N + 1) * sizeof(ApgdSched));
+    L.st.step = (float*)take(row); L.st.loss_best = (float*)take(row); L.st.loss_best_last = (float*)take(row);
+    L.st.reduced_last = (int32_t*)take(row); L.st.robust = (int32_t*)take(row); L.st.flags = (uint32_t*)take(row);
+    L.st.tr_loss = (float*)take((size_t)(N + 1) * row); L.st.tr_step = (float*)take((size_t)N * row);
+    L.st.tr_pred = (int32_t*)take((size_t)(N + 1) * row);
+    return off;
+}
+static int apgd_check_scratch(const vl_model* m, const void* scratch, size_t bytes, int batch, int steps) {
+    if (!m->main.ws.max_batch) return fail(VL_ERR_STATE, "no workspace");
+    if (batch <= 0 || batch > m->main.ws.max_batch) return fail(VL_ERR_STATE, "batch exceeds planned workspace");
+    if (batch > 65535) return fail(VL_ERR_UNSUPPORTED, "APGD runs at most 65535 images per call (one grid row per image)");
+    if (steps < 1 || steps > 65535) return fail(VL_ERR_ARG, "steps must be 1 .. 65535");
+    if (!scratch || ((uintptr_t)scratch & 255)) return fail(VL_ERR_ARG, "scratch must be a 256-byte aligned device buffer");
+    ApgdLayout sz;
+    const size_t need = apgd_carve(m, batch, steps, nullptr, sz);
+    if (bytes < need) return fail(VL_ERR_ARG, "APGD scratch too small: %zu < %zu (vl_apgd_scratch_bytes)", bytes, need);
+    return VL_OK;
+}
+
+int vl_apgd_scratch_bytes(vl_model* m, int batch, int steps, size_t* bytes) {
+    if (!m || !bytes || batch <= 0 || steps < 1 || steps > 65535) return fail(VL_ERR_ARG, "bad argument");
+    ApgdLayout sz;
+    *bytes = apgd_carve(m, batch, steps, nullptr, sz);
+    return VL_OK;
+}
+
+// one APGD iteration in the main pass: evaluate x_adv (forward, CE, gradient to grad_img), then bookkeeping and the next point
+static int apgd_iteration(vl_model* m, const ApgdLayout& L, int B, int N, float eps, float rho, hipStream_t s) {
+    Pass& p = m->main;
+    int rc = forward_impl(m, p, L.x_adv, B, 1, 0, s);
+    if (rc) return rc;
+    k_ce_loss(p.ws.logits, L.labels, B, m->C, p.ws.dlogits, p.ws.loss_img, p.ws.loss, m->err_flag, s);
+    p.have_loss = 1;
+    if ((rc = backward_impl(m, p, p.ws.grad_img, nullptr, s))) return rc;
+    k_apgd_track(L.st, p.ws.loss_img, p.ws.logits, L.labels, B, m->C, N, eps, rho, s);
+    k_apgd_step(L.x_adv, L.x_old, L.x_best, L.x_best_adv, L.grad_best, L.x0, p.ws.grad_img, L.st.flags, L.st.step, B,
+                (int64_t)3 * m->S * m->S, eps, L.st.sched, L.st.ctr, N, 0.f, 0, s, m->err_flag);
+    return VL_OK;
+}
+
+int vl_apgd_attack(vl_model* m, const vl_apgd_args* a) {
+    if (!m || !a || !a->x0 || !a->labels) return fail(VL_ERR_ARG, "bad argument");
+    if (!(a->eps >= 0.f) || !(a->eps < INFINITY) || !(a->rho >= 0.f) || !(a->rho <= 1.f)) return fail(VL_ERR_ARG, "eps must be finite and >= 0, rho in [0, 1]");
+    int rc = apgd_check_scratch(m, a->scratch, a->scratch_bytes, a->batch, a->steps);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)a->stream;
+    if ((rc = check_async(m))) return rc;
+    if (m->dirty && (rc = vl_lora_commit(m, a->stream))) return rc;     // the attack sees the CURRENT adapters
+    const int B = a->batch, N = a->steps;
+    const float eps = a->eps, rho = a->rho;
+    ApgdLayout L;
+    apgd_carve(m, B, N, (char*)a->scratch, L);
+    const int64_t n_img = (int64_t)3 * m->S * m->S, n = (int64_t)B * n_img;
+    // staging, as vl_pgd_attack: the captured iteration only ever sees addresses inside the scratch and the workspace
+    HIPCHK(hipMemcpyAsync(L.x0, a->x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(L.labels, a->labels, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    if (a->x_init) k_apgd_start(L.x_adv, a->x_init, n, s);
+    else if (a->random_start) k_apgd_rand_init(L.x_adv, L.x0, eps, a->seed, B, n_img, s);
+    else k_apgd_start(L.x_adv, L.x0, n, s);
+    HIPCHK(hipMemcpyAsync(L.x_old, L.x_adv, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    k_apgd_sched(L.st.sched, L.st.ctr, N, s);
+    m->fwd_chains = 0;
+    if (!m->use_graph || g_prof || g_poison_lds) {
+        for (int j = 0; j <= N; ++j)
+            if ((rc = apgd_iteration(m, L, B, N, eps, rho, s))) return rc;
+        if ((rc = check_launch("vl_apgd_attack"))) return rc;
+    } else {
+        hipGraphExec_t exec = nullptr;
+        for (GraphEntry& g : m->graphs)
+            if (g.kind == 1 && g.B == B && g.eps == eps && g.steps == N && g.scratch == a->scratch && g.rho == rho) { exec = g.exec; break; }
+        if (!exec) {      // captured cold on the private stream, as the PGD iteration
+            if (!m->cap_stream) HIPCHK(hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking));
+            hipGraph_t graph = nullptr;
+            (void)hipGetLastError();
+            HIPCHK(hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeThreadLocal));
+            const int rcc = apgd_iteration(m, L, B, N, eps, rho, m->cap_stream);
+            hipError_t e = hipStreamEndCapture(m->cap_stream, &graph);
+            if (rcc) { if (graph) (void)hipGraphDestroy(graph); return rcc; }
+            if (e != hipSuccess) return fail(VL_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
+            dump_graph(graph);
+            e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+            (void)hipGraphDestroy(graph);
+            if (e != hipSuccess) return fail(VL_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
+            GraphEntry ge = {B, eps, 0.f, exec, 1, nullptr};
+            ge.kind = 1; ge.steps = N; ge.scratch = a->scratch; ge.rho = rho;
+            remember_graph(m, ge);
+        }
+        for (int j = 0; j <= N; ++j) HIPCHK(hipGraphLaunch(exec, s));
+    }
+    const size_t row = (size_t)B * 4;
+    if (a->x_best) HIPCHK(hipMemcpyAsync(a->x_best, L.x_best, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (a->x_best_adv) HIPCHK(hipMemcpyAsync(a->x_best_adv, L.x_best_adv, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (a->loss_best) HIPCHK(hipMemcpyAsync(a->loss_best, L.st.loss_best, row, hipMemcpyDeviceToDevice, s));
+    if (a->robust) HIPCHK(hipMemcpyAsync(a->robust, L.st.robust, row, hipMemcpyDeviceToDevice, s));
+    if (a->trace_loss) HIPCHK(hipMemcpyAsync(a->trace_loss, L.st.tr_loss, (size_t)(N + 1) * row, hipMemcpyDeviceToDevice, s));
+    if (a->trace_step) HIPCHK(hipMemcpyAsync(a->trace_step, L.st.tr_step, (size_t)N * row, hipMemcpyDeviceToDevice, s));
+    if (a->trace_pred) HIPCHK(hipMemcpyAsync(a->trace_pred, L.st.tr_pred, (size_t)(N + 1) * row, hipMemcpyDeviceToDevice, s));
+    return VL_OK;
+}
+
+int vl_debug_apgd_track(vl_model* m, const vl_apgd_track_case* c, void* stream) {
+    if (!m || !c || !c->loss_img || !c->logits || !c->labels) return fail(VL_ERR_ARG, "bad argument");
+    int rc = apgd_check_scratch(m, c->scratch, c->scratch_bytes, c->batch, c->steps);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ApgdLayout L;
+    apgd_carve(m, c->batch, c->steps, (char*)c->scratch, L);
+    if (c->reset) k_apgd_sched(L.st.sched, L.st.ctr, c->steps, s);
+    k_apgd_track(L.st, c->loss_img, c->logits, c->labels, c->batch, m->C, c->steps, c->eps, c->rho, s);
+    HIPCHK(hipMemcpyAsync(L.st.ctr, L.st.ctr + 1, 4, hipMemcpyDeviceToDevice, s));      // what the step kernel does in the attack
+    const size_t row = (size_t)c->batch * 4;
+    if (c->step_out) HIPCHK(hipMemcpyAsync(c->step_out, L.st.step, row, hipMemcpyDeviceToDevice, s));
+    if (c->flags_out) HIPCHK(hipMemcpyAsync(c->flags_out, L.st.flags, row, hipMemcpyDeviceToDevice, s));
+    if (c->loss_best_out) HIPCHK(hipMemcpyAsync(c->loss_best_out, L.st.loss_best, row, hipMemcpyDeviceToDevice, s));
+    if (c->robust_out) HIPCHK(hipMemcpyAsync(c->robust_out, L.st.robust, row, hipMemcpyDeviceToDevice, s));
+    return VL_OK;
+}
+
+#ifndef VL_BF16
+int vl_apgd_step(float* x_adv, float* x_old, float* x_best, float* x_best_adv, float* grad_best, const float* x0,
+                 const float* grad, const uint32_t* flags, const float* step, int batch, int64_t image_elems, float eps,
+                 float a, int last, void* stream) {
+    if (!x_adv || !x_old || !x_best || !x_best_adv || !grad_best || !x0 || !grad || !flags || !step || batch <= 0 || batch > 65535 ||
+        image_elems <= 0 || image_elems % 4)
+        return fail(VL_ERR_ARG, "bad argument (image_elems must be a positive multiple of 4, batch 1 .. 65535)");
+    const void* ptrs[] = {x_adv, x_old, x_best, x_best_adv, grad_best, x0, grad};
+    for (const void* p : ptrs)
+        if ((uintptr_t)p & 15) return fail(VL_ERR_ARG, "image pointers must be 16-byte aligned");
+    k_apgd_step(x_adv, x_old, x_best, x_best_adv, grad_best, x0, grad, flags, step, batch, image_elems, eps, nullptr, nullptr, 0, a,
+                last ? 1 : 0, (hipStream_t)stream);
+    return VL_OK;
+}
+#endif
 
 #ifndef VL_BF16
 int vl_adam_step(float* param, const float* grad, float* m1, float* m2, float lr, float b1, float b2, float eps, int t,

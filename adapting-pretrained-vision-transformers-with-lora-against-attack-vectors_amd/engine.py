@@ -292,6 +292,88 @@ class Engine:
         self._keep, self._keep_labels = x0, labels
         return adv
 
+    # -- Auto-PGD (APGD-CE, L-inf) -------------------------------------------------------------------
+    def apgd_scratch_bytes(self, batch: int, steps: int) -> int:
+        n = C.c_size_t()
+        check(self.lib.vl_apgd_scratch_bytes(self.h, int(batch), int(steps), C.byref(n)), "vl_apgd_scratch_bytes")
+        return n.value
+
+    def _apgd_scratch(self, batch: int, steps: int):
+        """The attack's image state (about 6 image batches) as one tensor cached per (batch, steps): the same address on every
+        call, so the captured iteration is reused."""
+        cache = self.__dict__.setdefault("_apgd_scratch_cache", {})
+        key = (int(batch), int(steps))
+        if key not in cache:
+            while len(cache) >= 2:                 # a full batch and a ragged last one; 1.1 GB each at batch 256
+                cache.pop(next(iter(cache)))
+            n = self.apgd_scratch_bytes(batch, steps)
+            buf = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
+            cache[key] = (buf, (buf.data_ptr() + 255) // 256 * 256, n)
+        else:
+            cache[key] = cache.pop(key)            # most recently used last
+        return cache[key]
+
+    def apgd_attack(self, x0: torch.Tensor, labels: torch.Tensor, eps, steps=100, rho=0.75, x_init: Optional[torch.Tensor] = None,
+                    random_start=False, seed=0, trace=False, scratch=None) -> Dict[str, torch.Tensor]:
+        """vl_apgd_attack.  Returns {"x_best", "x_best_adv", "loss_best" [B], "robust" [B] bool} and with trace=True also
+        {"trace_loss" [steps+1, B], "trace_step" [steps, B], "trace_pred" [steps+1, B] bool}.
+        scratch: (base pointer, bytes) of a caller-owned buffer instead of the cached one (tests)."""
+        x0 = self._check_images(x0)
+        labels = labels.to(device=self.device, dtype=torch.int64).contiguous()
+        B, steps = x0.shape[0], int(steps)
+        self.plan(B, False)
+        if scratch is None:
+            _, base, nbytes = self._apgd_scratch(B, steps)
+        else:
+            base, nbytes = scratch
+        xi = self._check_images(x_init) if x_init is not None else None
+        if xi is not None and xi.shape != x0.shape:
+            raise ValueError("x_init must have the shape of the images")
+        out = {"x_best": torch.empty_like(x0), "x_best_adv": torch.empty_like(x0),
+               "loss_best": torch.empty(B, dtype=torch.float32, device=self.device),
+               "robust": torch.empty(B, dtype=torch.int32, device=self.device)}
+        if trace:
+            out["trace_loss"] = torch.empty(steps + 1, B, dtype=torch.float32, device=self.device)
+            out["trace_step"] = torch.empty(steps, B, dtype=torch.float32, device=self.device)
+            out["trace_pred"] = torch.empty(steps + 1, B, dtype=torch.int32, device=self.device)
+        a = _lib.VLApgdArgs()
+        a.x0, a.labels, a.batch, a.steps = x0.data_ptr(), labels.data_ptr(), B, steps
+        a.eps, a.rho = float(eps), float(rho)
+        a.x_init = xi.data_ptr() if xi is not None else None
+        a.random_start, a.seed = int(bool(random_start)), int(seed) & (2 ** 64 - 1)
+        a.scratch, a.scratch_bytes = base, nbytes
+        for k, t in out.items():
+            setattr(a, k, t.data_ptr())
+        a.stream = self._stream().value
+        check(self.lib.vl_apgd_attack(self.h, C.byref(a)), "vl_apgd_attack")
+        self._keep, self._keep_labels, self._keep_init = x0, labels, xi
+        out["robust"] = out["robust"] != 0
+        if trace:
+            out["trace_pred"] = out["trace_pred"] != 0
+        return out
+
+    def apgd_step(self, x_adv, x_old, x_best, x_best_adv, grad_best, x0, grad, flags, step, eps, a, last=False):
+        """vl_apgd_step on caller tensors: [B, ...] fp32 images (updated in place), flags [B] int32, step [B] fp32."""
+        B = x_adv.shape[0]
+        check(self.lib.vl_apgd_step(*[C.c_void_p(t.data_ptr()) for t in (x_adv, x_old, x_best, x_best_adv, grad_best, x0, grad,
+                                                                        flags, step)],
+                                    B, x_adv.numel() // B, float(eps), float(a), int(bool(last)), self._stream()), "vl_apgd_step")
+
+    def apgd_track(self, scratch, batch, steps, eps, rho, loss_img, logits, labels, reset=False):
+        """vl_debug_apgd_track: one call of the bookkeeping kernel on `scratch` = (base pointer, bytes); returns
+        (step [B], flags [B] int32, loss_best [B], robust [B] int32) as left by that call."""
+        c = _lib.VLApgdTrackCase()
+        c.scratch, c.scratch_bytes = scratch
+        c.batch, c.steps, c.reset, c.eps, c.rho = int(batch), int(steps), int(bool(reset)), float(eps), float(rho)
+        c.loss_img, c.logits, c.labels = loss_img.data_ptr(), logits.data_ptr(), labels.data_ptr()
+        step = torch.empty(batch, dtype=torch.float32, device=self.device)
+        flags = torch.empty(batch, dtype=torch.int32, device=self.device)
+        best = torch.empty(batch, dtype=torch.float32, device=self.device)
+        robust = torch.empty(batch, dtype=torch.int32, device=self.device)
+        c.step_out, c.flags_out, c.loss_best_out, c.robust_out = step.data_ptr(), flags.data_ptr(), best.data_ptr(), robust.data_ptr()
+        check(self.lib.vl_debug_apgd_track(self.h, C.byref(c), self._stream()), "vl_debug_apgd_track")
+        return step, flags, best, robust
+
     def channel_affine(self, x: torch.Tensor, scale, shift, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         x = self._check_images(x)
         out = torch.empty_like(x) if out is None else out
@@ -384,6 +466,21 @@ class Engine:
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != S or x.shape[3] != S:
             raise ValueError(f"expected images of shape [B,3,{S},{S}], got {tuple(x.shape)}")
         return self._f32(x)
+
+
+def apgd_schedule(n_iter: int):
+    """Checkpoints of Auto-PGD for n_iter iterations as (i, k) pairs: iteration i ends a window of k iterations
+    (k0 = max(int(.22 N), 1), shrinking by max(int(.03 N), 1) down to max(int(.06 N), 1)).  The library builds the same table on
+    the device (csrc/elementwise.hip: apgd_sched_kernel)."""
+    n = int(n_iter)
+    k, k_min, dec = max(int(0.22 * n), 1), max(int(0.06 * n), 1), max(int(0.03 * n), 1)
+    out, cnt = [], 0
+    for i in range(n):
+        cnt += 1
+        if cnt == k:
+            out.append((i, k))
+            k, cnt = max(k - dec, k_min), 0
+    return out
 
 
 def module_shape(arch: ArchConfig, target: str) -> Tuple[int, int]:

@@ -193,6 +193,67 @@ int vl_pgd_attack(vl_model* m, const float* x0, const int64_t* labels, int batch
                   float eps, float alpha, int steps, int random_start, uint64_t seed,
                   float* adv_out, void* stream);
 
+/* ---- Auto-PGD on cross-entropy, L-inf (APGD-CE): the first component of AutoAttack(model, norm='Linf', eps, version='standard'),
+ * which auto_attack.py:98-108 runs.  The algorithm is the restatement in DESIGN.md section 3.9 and tests/apgd_ref.py, written from
+ * memory of the autoattack package's autopgd_base.py (not installed here): PARITY WITH THE PACKAGE IS UNPINNED.
+ * One iteration (forward, CE, backward to the input, apgd_track_kernel, apgd_step_kernel) is captured once and replayed steps + 1
+ * times (replay 0 evaluates the start point).  Step size, best loss, best point, momentum point and the checkpoint bookkeeping
+ * live per image on the device, the iteration index in a device-side counter: no device-to-host copy, no stream synchronisation.
+ * One chain only.  The model is fed normalised pixels as in vl_pgd_attack.
+ * ALL image state lives in `scratch` (vl_apgd_scratch_bytes; 256-byte aligned, the only memory besides the workspace that the call
+ * writes; results do not depend on what it held): x_adv, x_old, x_best, x_best_adv, grad_best, the staged x0 and labels, the
+ * per-image scalars, the schedule table and the trace -- about 6 image batches.  vl_plan and the workspace are unchanged. */
+typedef struct vl_apgd_args {
+    const float* x0;          /* [B,3,S,S] fp32 in [0,1] */
+    const int64_t* labels;    /* [B] */
+    int32_t batch;
+    int32_t steps;            /* n_iter >= 1 */
+    float eps;
+    float rho;                /* .75 */
+    const float* x_init;      /* NULL, or the start point [B,3,S,S] (clamped to [0,1], NOT projected; random_start is ignored) */
+    int32_t random_start;     /* x_init == NULL: 0 = start at x0, else x0 + eps t / max|t|, t ~ U(-1,1) (counter-based, per-image max) */
+    int32_t reserved0;
+    uint64_t seed;
+    void* scratch;
+    size_t scratch_bytes;
+    /* outputs, each may be NULL */
+    float* x_best;            /* [B,3,S,S] the maximum-loss point (adversarial training) */
+    float* x_best_adv;        /* [B,3,S,S] the latest misclassified point; the start point for an image that was never fooled */
+    float* loss_best;         /* [B] per-image CE at x_best */
+    int32_t* robust;          /* [B] 1 = classified as its label at the start point and after every iteration */
+    /* optional trace */
+    float* trace_loss;        /* [steps + 1][B] row 0 = the start point, row i + 1 = the point of iteration i */
+    float* trace_step;        /* [steps][B] the step size iteration i's update used */
+    int32_t* trace_pred;      /* [steps + 1][B] argmax == label */
+    void* stream;
+    int32_t reserved[4];
+} vl_apgd_args;
+int vl_apgd_scratch_bytes(vl_model* m, int batch, int steps, size_t* bytes);
+int vl_apgd_attack(vl_model* m, const vl_apgd_args* args);
+
+/* One launch of apgd_step_kernel on CALLER-OWNED buffers (tests): per image b of `image_elems` floats (a multiple of 4; every
+ * pointer 16-byte aligned), with flags[b] = 1 improved | 2 fooled | 4 restart and the step size step[b]:
+ *   improved: x_best, grad_best <- x_adv, grad;  fooled: x_best_adv <- x_adv;  restart (and not improved): x_adv, grad <- x_best, grad_best;
+ *   last == 0:  g2 = x_adv - x_old;  x_old <- x_adv;  z = P(x_adv + step sign(grad));  x_adv <- P((x_adv + (z - x_adv) a) + g2 (1 - a)),
+ *   P(v) = clamp(min(max(v, x0 - eps), x0 + eps), 0, 1), every operation rounded to fp32 on its own;  last != 0: copies only. */
+int vl_apgd_step(float* x_adv, float* x_old, float* x_best, float* x_best_adv, float* grad_best, const float* x0,
+                 const float* grad, const uint32_t* flags, const float* step, int batch, int64_t image_elems, float eps,
+                 float a, int last, void* stream);
+
+/* One launch of apgd_track_kernel (tests): the state lives in `scratch` as in vl_apgd_attack (sized for batch, steps).  reset != 0
+ * first builds the schedule table and zeroes the iteration counter; each call then consumes one iteration index (call j = replay j:
+ * 0 = the start point, j = the point of iteration j - 1) from loss_img [B], logits [B][num_labels] and labels [B], and copies out
+ * what the kernel left: step_out [B], flags_out [B] (1 improved | 2 fooled | 4 restart), loss_best_out [B], robust_out [B]
+ * (each may be NULL). */
+typedef struct vl_apgd_track_case {
+    void* scratch; size_t scratch_bytes;
+    int32_t batch, steps, reset, reserved0;
+    float eps, rho;
+    const float* loss_img; const float* logits; const int64_t* labels;
+    float* step_out; uint32_t* flags_out; float* loss_best_out; int32_t* robust_out;
+} vl_apgd_track_case;
+int vl_debug_apgd_track(vl_model* m, const vl_apgd_track_case* c, void* stream);
+
 /* optimizer.step() of torch.optim.Adam(lr, betas, eps) (train_loras.py:284,315) on a
  * flat buffer; t = 1-based step count. */
 int vl_adam_step(float* param, const float* grad, float* m1, float* m2, float lr, float b1,
