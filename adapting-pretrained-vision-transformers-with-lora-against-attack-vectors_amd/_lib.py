@@ -150,6 +150,39 @@ SIGNATURES.update({
 })
 
 
+class VLSquareArgs(C.Structure):
+    """vl_square_args of include/vitlora.h (field for field)."""
+    _fields_ = [
+        ("x0", C.c_void_p), ("labels", C.c_void_p), ("batch", C.c_int32), ("n_queries", C.c_int32),
+        ("first", C.c_int32), ("count", C.c_int32), ("eps", C.c_float), ("p_init", C.c_float),
+        ("seed", C.c_uint64), ("image_offset", C.c_uint64),
+        ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t),
+        ("x_best", C.c_void_p), ("margin_min", C.c_void_p), ("queries", C.c_void_p), ("robust", C.c_void_p),
+        ("trace_margin", C.c_void_p), ("trace_win", C.c_void_p),
+        ("stream", C.c_void_p), ("reserved", C.c_int32 * 4),
+    ]
+
+
+class VLSquareTrackCase(C.Structure):
+    """vl_square_track_case of include/vitlora.h (field for field)."""
+    _fields_ = [
+        ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t),
+        ("batch", C.c_int32), ("n_queries", C.c_int32), ("reset", C.c_int32), ("reserved0", C.c_int32),
+        ("p_init", C.c_float), ("reserved1", C.c_float), ("seed", C.c_uint64), ("image_offset", C.c_uint64),
+        ("logits", C.c_void_p), ("labels", C.c_void_p),
+        ("flags_out", C.c_void_p), ("win_prev_out", C.c_void_p), ("win_next_out", C.c_void_p),
+        ("margin_min_out", C.c_void_p), ("queries_out", C.c_void_p),
+    ]
+
+
+SIGNATURES.update({
+    "vl_square_scratch_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "vl_square_attack": (C.c_int, [C.c_void_p, C.POINTER(VLSquareArgs)]),
+    "vl_square_step": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "vl_debug_square_track": (C.c_int, [C.c_void_p, C.POINTER(VLSquareTrackCase), C.c_void_p]),
+})
+
+
 class VLSwinConfig(C.Structure):
     _fields_ = [("image_size", C.c_int32), ("patch_size", C.c_int32), ("embed_dim", C.c_int32), ("depths", C.c_int32 * 4),
                 ("heads", C.c_int32 * 4), ("window", C.c_int32), ("num_labels", C.c_int32), ("ln_eps", C.c_float),

@@ -169,35 +169,92 @@ class APGD(_Attack):
         return self._finish(eng, adv)
 
 
+def _square(eng, x, labels, eps, n_queries, p_init, n_restarts, seed, image_offset=0, check_every=0):
+    """Square with restarts on [0,1] images (the engine's normalisation is the caller's to set): an image that is classified
+    correctly before the attack takes x_best of the first restart that fools it (restart r uses seed + r).  Returns
+    (adv, still_robust [B] bool, clean_correct [B] bool, result of the last restart)."""
+    labels = labels.to(device=eng.device, dtype=torch.int64)
+    correct = eng.forward(x, normalise=True).argmax(1) == labels
+    robust = correct.clone()
+    adv = x.clone()
+    res = None
+    for r in range(max(1, int(n_restarts))):
+        res = eng.square_attack(x, labels, eps, n_queries, p_init=p_init, seed=int(seed) + r, image_offset=image_offset,
+                                check_every=check_every)
+        take = robust & ~res["robust"]
+        adv = torch.where(take.view(-1, 1, 1, 1), res["x_best"], adv)
+        robust = robust & res["robust"]
+    return adv, robust, correct, res
+
+
+class Square(_Attack):
+    """torchattacks.Square(model, norm='Linf', eps, n_queries, n_restarts, p_init, loss='margin', resc_schedule, seed): the
+    score-based random-search attack of Andriushchenko et al. 2020, the whole loop on the device (vl_square_attack); it reads
+    logits only, no gradient.  The algorithm is the library's restatement of the autoattack package's square.py from memory
+    (include/vitlora.h): parity with the package is unpinned.  Two deliberate deviations: the window and
+    its signs are drawn per image (the package: one window per batch), and the window is written as clamp(x0 +- eps, 0, 1)
+    directly.  Restart r uses seed + r; an image takes the point of the first restart that fools it.  After a call `last`
+    holds the last restart's x_best / margin_min / queries / robust."""
+
+    def __init__(self, model, norm="Linf", eps=8 / 255, n_queries=5000, n_restarts=1, p_init=0.8, loss="margin",
+                 resc_schedule=True, seed=0):
+        super().__init__(model)
+        if norm != "Linf":
+            raise ValueError(f"Square: only norm='Linf' is built (got {norm!r})")
+        if loss != "margin":
+            raise ValueError(f"Square: only loss='margin' is built (got {loss!r})")
+        if not resc_schedule:
+            raise ValueError("Square: only the rescaled schedule (resc_schedule=True) is built")
+        self.norm, self.eps, self.n_queries, self.n_restarts, self.p_init = norm, eps, n_queries, n_restarts, p_init
+        self.loss, self.resc_schedule, self.seed = loss, resc_schedule, seed
+        self.last = None
+
+    def forward(self, images, labels):
+        vit, eng, x = self._prepare(images)
+        if self._norm is None:
+            eng.set_normalization([0.0, 0.0, 0.0], [1.0, 1.0, 1.0])
+        adv, _, _, self.last = _square(eng, x, labels, self.eps, self.n_queries, self.p_init, self.n_restarts, self.seed)
+        if self._norm is None:
+            from .engine import IMAGENET_MEAN, IMAGENET_STD
+            eng.set_normalization(IMAGENET_MEAN, IMAGENET_STD)   # back to the library default
+        return self._finish(eng, adv)
+
+
 class AutoAttack:
     """autoattack.AutoAttack(model, norm='Linf', eps, version, attacks_to_run, seed) as auto_attack.py:98-108 uses it.
-    Only the first component of the standard suite, APGD-CE, is built: version='custom' with attacks_to_run=['apgd-ce'] runs
-    it; version='standard' raises NotImplementedError.  Images are in [0,1]; the model is fed (x - mean) / std (the reference
-    wraps its model in a NormalizedModel, auto_attack.py:47-55), ImageNet constants unless `mean` / `std` are given."""
+    Of the standard suite (APGD-CE, APGD-T, FAB-T, Square) the first and the last component are built: version='custom' runs any
+    non-empty ordered subset of ['apgd-ce', 'square'], each component's result taken only for the images that are still robust;
+    version='standard' raises NotImplementedError (APGD-T and FAB-T are missing).  Images are in [0,1]; the model is fed
+    (x - mean) / std (the reference wraps its model in a NormalizedModel, auto_attack.py:47-55), ImageNet constants unless
+    `mean` / `std` are given.  Square draws per image from (seed, index of the image in x_orig): its result does not depend on bs."""
 
-    MISSING = ("apgd-t", "fab-t", "square")
+    BUILT = ("apgd-ce", "square")
+    MISSING = ("apgd-t", "fab-t")
 
     def __init__(self, model, norm="Linf", eps=0.3, version="standard", attacks_to_run=(), seed=None, device=None, verbose=False,
-                 steps=100, n_restarts=1, rho=0.75, mean=None, std=None):
+                 steps=100, n_restarts=1, rho=0.75, mean=None, std=None, square_queries=5000, p_init=0.8, check_every=0):
         if norm != "Linf":
             raise ValueError(f"AutoAttack: only norm='Linf' is built (got {norm!r})")
         if version == "standard":
-            raise NotImplementedError("AutoAttack(version='standard') needs APGD-T, FAB-T and Square, which are not built; "
-                                      "use version='custom', attacks_to_run=['apgd-ce']")
+            raise NotImplementedError("AutoAttack(version='standard'): the standard suite runs APGD-T, FAB-T and Square after APGD-CE; "
+                                      "APGD-T and FAB-T are not built; use version='custom', attacks_to_run=['apgd-ce', 'square']")
         if version != "custom":
             raise ValueError(f"AutoAttack: version must be 'standard' or 'custom' (got {version!r})")
-        bad = [a for a in attacks_to_run if a != "apgd-ce"]
-        if bad or not list(attacks_to_run):
-            raise NotImplementedError(f"AutoAttack: attacks_to_run must be ['apgd-ce'] (not built: {bad})")
-        self.model, self.norm, self.eps, self.version, self.attacks_to_run = model, norm, eps, version, list(attacks_to_run)
+        run = list(attacks_to_run)
+        bad = [a for a in run if a not in self.BUILT]
+        if bad or not run or len(set(run)) != len(run):
+            raise NotImplementedError(f"AutoAttack: attacks_to_run must be a non-empty subset of {list(self.BUILT)} (not built: {bad})")
+        self.model, self.norm, self.eps, self.version, self.attacks_to_run = model, norm, eps, version, run
         self.seed = 0 if seed is None else int(seed)
         self.steps, self.n_restarts, self.rho = steps, n_restarts, rho
+        self.square_queries, self.p_init, self.check_every = square_queries, p_init, check_every
         from .engine import IMAGENET_MEAN, IMAGENET_STD
         self.mean = [float(v) for v in (mean if mean is not None else IMAGENET_MEAN)]
         self.std = [float(v) for v in (std if std is not None else IMAGENET_STD)]
         self.robust_accuracy = None
 
-    def run_standard_evaluation(self, x_orig, y_orig, bs=250):
+    def run_standard_evaluation(self, x_orig, y_orig, bs=250, image_offset=0):
+        """image_offset: the index of x_orig[0] in the data set when a caller feeds the set in several calls (Square only)."""
         vit = _unwrap(self.model)
         eng = vit._engine()
         vit.sync_params()
@@ -207,11 +264,23 @@ class AutoAttack:
         out, n_robust = [], 0
         for lo in range(0, x_all.shape[0], int(bs)):
             x, y = x_all[lo:lo + bs], y_all[lo:lo + bs]
-            adv, robust, _, _ = _apgd_ce(eng, x, y, self.eps, self.steps, self.rho, self.n_restarts, self.seed)
+            adv = robust = None
+            for name in self.attacks_to_run:
+                if name == "apgd-ce":
+                    a, r, _, _ = _apgd_ce(eng, x, y, self.eps, self.steps, self.rho, self.n_restarts, self.seed)
+                else:
+                    a, r, _, _ = _square(eng, x, y, self.eps, self.square_queries, self.p_init, self.n_restarts, self.seed,
+                                         image_offset=int(image_offset) + lo, check_every=self.check_every)
+                if adv is None:
+                    adv, robust = a, r
+                else:             # only for the images the earlier components left robust (r is False for clean-wrong images too)
+                    take = robust & ~r
+                    adv = torch.where(take.view(-1, 1, 1, 1), a, adv)
+                    robust = robust & r
             out.append(adv)
             n_robust += int(robust.sum().item())
         self.robust_accuracy = n_robust / max(1, x_all.shape[0])
         return torch.cat(out)
 
 
-__all__ = ["batched_fgsm_attack", "FGSM", "PGD", "APGD", "AutoAttack", "LogitsModel"]
+__all__ = ["batched_fgsm_attack", "FGSM", "PGD", "APGD", "Square", "AutoAttack", "LogitsModel"]

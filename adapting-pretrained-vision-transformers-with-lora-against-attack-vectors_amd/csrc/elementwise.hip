@@ -3,6 +3,7 @@
 // flat Adam (K12), the save_images quantiser and the weight packers.
 // Every kernel moves 16 bytes per lane wherever the layout allows it.
 #include <algorithm>
+#include <cmath>
 
 #include "kernels.h"
 #include "prof.h"
@@ -973,6 +974,167 @@ __global__ __launch_bounds__(256) void apgd_step_kernel(float* __restrict__ x_ad
     }
 }
 
+// ---------------------------------------------------------------------------------
+// Square attack (Andriushchenko et al. 2020; L-inf, untargeted margin loss, rescaled schedule).  The algorithm is the restatement
+// in DESIGN.md section 3.10 -- written from memory of the autoattack package's square.py and the paper, neither installed here:
+// parity with the package is UNPINNED.  Two deliberate deviations: the window and its signs are drawn PER IMAGE (an image's
+// random stream depends on its global index alone, not on its neighbours or the batch cut), and the window is written as
+// clamp(x0 +- eps, 0, 1) directly.  One captured iteration (eval forward of x_cur, square_track_kernel, square_step_kernel)
+// serves every replay; the replay index is the two-word counter of the APGD kernels above (the track kernel reads ctr[0] and
+// writes ctr[1], the step kernel reads ctr[1] and writes ctr[0]).  Seed and image offset are read from the scratch, not passed
+// as arguments, so one captured iteration serves every seed.
+//   r(g, j, k) = mix64(key ^ (g << 32) ^ (j << 2) ^ k),  g = the image's global index, k = 0 row, 1 column, 2 signs, 3 stripes
+// ---------------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t square_draw(uint64_t key, uint64_t g, uint32_t j, uint32_t k) {
+    return mix64(key ^ (g << 32) ^ ((uint64_t)j << 2) ^ (uint64_t)k);
+}
+
+// side[j] of proposal j = 1 .. N from the (first proposal, side) pairs; the counter; key and image offset
+__global__ __launch_bounds__(256) void square_sched_kernel(SquareState st, SquareSched sc, int N, uint64_t seed, uint64_t offset) {
+    for (int j = threadIdx.x; j <= N; j += 256) {
+        int k = 0;
+#pragma unroll
+        for (int i = 1; i < 10; ++i) k = j >= sc.from[i] ? i : k;
+        st.side[j] = sc.side[k];
+    }
+    if (threadIdx.x == 0) {
+        st.ctr[0] = 0; st.ctr[1] = 0; st.ctr[2] = 0; st.ctr[3] = 0;
+        st.par->key = seed * 0xD1342543DE82EF95ull;
+        st.par->offset = offset;
+    }
+}
+
+// the start point: vertical stripes, one sign per (image, channel, column), written into x_cur and x_best; blockIdx.y = image
+__global__ __launch_bounds__(256) void square_init_kernel(float* __restrict__ x_cur, float* __restrict__ x_best,
+                                                          const float* __restrict__ x0, const SquareParams* __restrict__ par,
+                                                          int S, float eps) {
+    const uint64_t key = par->key, g = par->offset + blockIdx.y;
+    const int n = 3 * S * S;
+    const int64_t base = (int64_t)blockIdx.y * n;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const int c = i / (S * S), col = i % S;
+        const bool up = (square_draw(key, g, (uint32_t)(c * S + col), 3) >> 40) & 1;
+        const float x = x0[base + i];
+        const float v = fminf(fmaxf(up ? x + eps : x - eps, 0.f), 1.f);
+        x_cur[base + i] = v;
+        x_best[base + i] = v;
+    }
+}
+
+// One replay's bookkeeping for one image per wave (four per block): the margin z_y - max_{j != y} z_j from the logits row,
+// accept / reject of the pending proposal, margin_min and the query count, then the next proposal unless the image is frozen
+// (margin_min <= 0) or this is the last replay.  A margin that is not finite is never accepted and raises the error word.
+__global__ __launch_bounds__(256) void square_track_kernel(SquareState st, const float* __restrict__ logits,
+                                                           const int64_t* __restrict__ labels, int B, int C, int S, int N,
+                                                           int* __restrict__ err) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int j = st.ctr[0];
+    if (blockIdx.x == 0 && threadIdx.x == 0) st.ctr[1] = j + 1;
+    if (b >= B || (unsigned)j > (unsigned)N) return;     // a replay past the schedule does nothing
+    const int64_t y = labels[b];
+    const bool ybad = y < 0 || y >= C;
+    const float* lr = logits + (int64_t)b * C;
+    float mx = -INFINITY;
+    int bad = 0;
+    for (int c = lane; c < C; c += 64) {
+        if (c == y) continue;
+        const float v = lr[c];
+        bad |= v != v;
+        mx = fmaxf(mx, v);
+    }
+    mx = wave_max(mx);
+    bad = __any(bad);
+    if (lane) return;
+    const float m = (ybad || bad) ? NAN : lr[y] - mx;
+    const bool finite = fabsf(m) < INFINITY;
+    if (!finite && err) *err = ybad ? 1 : 5;
+    float mm;
+    int q;
+    uint32_t fl = 0;
+    int32_t* const wp = st.win_prev + 4 * b;
+    int32_t* const wn = st.win_next + 4 * b;
+    if (j == 0) {                                // the stripes
+        mm = finite ? m : INFINITY;
+        q = 1;
+    } else {
+        mm = st.margin_min[b];
+        q = st.queries[b];
+        if (st.flags[b] & SQ_NEXT) {             // proposal j was made for this image: this replay evaluated it
+            ++q;
+            fl |= SQ_PREV;
+            wp[0] = wn[0]; wp[1] = wn[1]; wp[2] = wn[2]; wp[3] = wn[3];
+            if (finite && m < mm) {
+                mm = m;
+                fl |= SQ_ACCEPT;
+                st.tr_win[((int64_t)(j - 1) * B + b) * 4 + 3] |= 16;
+            }
+        }
+    }
+    if (j < N) {
+        int32_t* const tw = st.tr_win + ((int64_t)j * B + b) * 4;
+        if (mm > 0.f) {                          // still active: proposal j + 1
+            const uint64_t key = st.par->key, g = st.par->offset + (uint64_t)b;
+            const int s = st.side[j + 1];
+            const uint64_t span = (uint64_t)(S - s + 1);
+            const int h = (int)(((square_draw(key, g, (uint32_t)(j + 1), 0) >> 32) * span) >> 32);
+            const int w = (int)(((square_draw(key, g, (uint32_t)(j + 1), 1) >> 32) * span) >> 32);
+            const int sg = (int)((square_draw(key, g, (uint32_t)(j + 1), 2) >> 40) & 7);
+            wn[0] = h; wn[1] = w; wn[2] = s; wn[3] = sg;
+            tw[0] = h; tw[1] = w; tw[2] = s; tw[3] = sg | 8;
+            fl |= SQ_NEXT;
+        } else {
+            tw[0] = 0; tw[1] = 0; tw[2] = 0; tw[3] = 0;
+        }
+    }
+    st.margin_min[b] = mm; st.queries[b] = q; st.robust[b] = mm > 0.f ? 1 : 0; st.flags[b] = fl;
+    st.tr_margin[(int64_t)j * B + b] = m;
+}
+
+// The pixel pass of one replay: blockIdx.y = image, so the flag branches are uniform over the block.  Only the union of the
+// previous and the next window is touched (3 (s_prev^2 + s_next^2) work items, never the whole image).  Item t < 3 s_prev^2 is a
+// pixel of the previous window: its thread resolves it (accept: x_best <- x_cur; reject: x_cur <- x_best) and, where the pixel
+// also lies in the next window, writes the new value afterwards.  The remaining items are the pixels of the next window; those
+// inside the previous window are skipped -- their owner is the thread above -- so every pixel of the union has exactly one owner
+// and overlapping windows cannot race.  Windows start at any column and have any width: plain dword accesses.
+// A window that does not fit the image is ignored (vl_square_step takes windows from the caller).
+__global__ __launch_bounds__(256) void square_step_kernel(float* __restrict__ x_cur, float* __restrict__ x_best,
+                                                          const float* __restrict__ x0, const uint32_t* __restrict__ flags,
+                                                          const int32_t* __restrict__ win_prev, const int32_t* __restrict__ win_next,
+                                                          int S, float eps, int32_t* __restrict__ ctr, int N) {
+    if (ctr) {
+        const int j = ctr[1] - 1;
+        if ((unsigned)j > (unsigned)N) return;
+        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) ctr[0] = j + 1;
+    }
+    const int b = blockIdx.y;
+    const uint32_t fl = flags[b];
+    const bool acc = fl & SQ_ACCEPT;
+    int ph = win_prev[4 * b], pw = win_prev[4 * b + 1], ps = win_prev[4 * b + 2];
+    int nh = win_next[4 * b], nw = win_next[4 * b + 1], ns = win_next[4 * b + 2];
+    const int nsg = win_next[4 * b + 3];
+    if (!(fl & SQ_PREV) || ps <= 0 || ps > S || ph < 0 || pw < 0 || ph > S - ps || pw > S - ps) ps = 0;
+    if (!(fl & SQ_NEXT) || ns <= 0 || ns > S || nh < 0 || nw < 0 || nh > S - ns || nw > S - ns) ns = 0;
+    const int np = 3 * ps * ps, total = np + 3 * ns * ns;
+    const int64_t base = (int64_t)b * 3 * S * S;
+    for (int t = blockIdx.x * 256 + threadIdx.x; t < total; t += gridDim.x * 256) {
+        const bool first = t < np;
+        const int u = first ? t : t - np, s = first ? ps : ns;
+        const int c = u / (s * s), rem = u - c * s * s, r = rem / s;
+        const int row = (first ? ph : nh) + r, col = (first ? pw : nw) + (rem - r * s);
+        const int64_t i = base + ((int64_t)c * S + row) * S + col;
+        if (first) {
+            if (acc) x_best[i] = x_cur[i];
+            else x_cur[i] = x_best[i];
+            if (!(row >= nh && row < nh + ns && col >= nw && col < nw + ns)) continue;     // ns == 0: never inside
+        } else if (row >= ph && row < ph + ps && col >= pw && col < pw + ps) {
+            continue;
+        }
+        const float x = x0[i];
+        x_cur[i] = fminf(fmaxf(((nsg >> c) & 1) ? x + eps : x - eps, 0.f), 1.f);
+    }
+}
+
 __global__ void fill_random_h16_kernel(h16* __restrict__ dst, size_t n, uint64_t seed) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -1321,6 +1483,47 @@ void k_apgd_step(float* x_adv, float* x_old, float* x_best, float* x_best_adv, f
     const int per_img = nblk((n4 + 1) / 2, 256, std::max(1, 8192 / B));
     hipLaunchKernelGGL(apgd_step_kernel, dim3(per_img, B), dim3(256), 0, s, x_adv, x_old, x_best, x_best_adv, grad_best, x0, grad,
                        flags, step, n4, eps, sched, ctr, N, a, last, err);
+}
+// p = p_init / 2^k for the k thresholds that it = int((j - 1) / N * 10000) exceeds strictly; side = round-half-even(sqrt(p S S)),
+// all in double (p_init enters as the float the ABI carries).  from[k] = the first proposal that uses side[k], N + 1 if none.
+void square_schedule(int S, int N, float p_init, SquareSched* out) {
+    static const int thr[9] = {10, 50, 200, 500, 1000, 2000, 4000, 6000, 8000};
+    for (int i = 0; i < 10; ++i) {
+        const double p = (double)p_init / (double)(1 << i);
+        const double v = std::nearbyint(std::sqrt(p * S * S));
+        out->side[i] = std::min(S, std::max(1, (int)v));
+        out->from[i] = N + 1;
+    }
+    for (int j = N; j >= 1; --j) {
+        const int it = (int)((double)(j - 1) / (double)N * 10000.0);
+        int k = 0;
+        for (int i = 0; i < 9; ++i) k += it > thr[i] ? 1 : 0;
+        out->from[k] = j;
+    }
+    out->from[0] = 1;
+    for (int i = 8; i >= 1; --i) out->from[i] = std::min(out->from[i], out->from[i + 1]);     // a k the schedule jumps over
+}
+void k_square_sched(const SquareState& st, const SquareSched& sc, int N, uint64_t seed, uint64_t image_offset, hipStream_t s) {
+    hipLaunchKernelGGL(square_sched_kernel, dim3(1), dim3(256), 0, s, st, sc, N, seed, image_offset);
+}
+void k_square_init(float* x_cur, float* x_best, const float* x0, const SquareParams* par, int B, int S, float eps, hipStream_t s) {
+    ProfScope prof_("square_init_kernel", 0.0, (double)B * 3 * S * S * 12.0, s);
+    hipLaunchKernelGGL(square_init_kernel, dim3(nblk((int64_t)3 * S * S, 256, std::max(1, 4096 / B)), B), dim3(256), 0, s, x_cur,
+                       x_best, x0, par, S, eps);
+}
+void k_square_track(const SquareState& st, const float* logits, const int64_t* labels, int B, int C, int S, int N, hipStream_t s,
+                    int* err) {
+    ProfScope prof_("square_track_kernel", 0.0, (double)B * (C + 24) * 4.0, s);
+    hipLaunchKernelGGL(square_track_kernel, dim3((B + 3) / 4), dim3(256), 0, s, st, logits, labels, B, C, S, N, err);
+}
+void k_square_step(float* x_cur, float* x_best, const float* x0, const uint32_t* flags, const int32_t* win_prev,
+                   const int32_t* win_next, int B, int S, float eps, int32_t* ctr, int N, hipStream_t s) {
+    ProfScope prof_("square_step_kernel", 0.0, 0.0, s);      // the traffic depends on the windows: 3 (s_prev^2 + s_next^2) x 12 B at most
+    // the grid is fixed at capture for the largest pair of windows (4 items per thread there); later, smaller windows leave
+    // most blocks with nothing to do
+    const int per_img = nblk((int64_t)6 * S * S, 1024, std::max(1, 2048 / B));
+    hipLaunchKernelGGL(square_step_kernel, dim3(per_img, B), dim3(256), 0, s, x_cur, x_best, x0, flags, win_prev, win_next, S, eps,
+                       ctr, N);
 }
 void k_adam(float* p, const float* g, float* m, float* v, float lr, float b1, float b2, float eps, int t, int64_t n,
             hipStream_t s, int* err) {

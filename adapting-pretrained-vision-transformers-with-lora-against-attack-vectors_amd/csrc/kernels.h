@@ -78,6 +78,38 @@ void k_apgd_track(const ApgdState& st, const float* loss_img, const float* logit
 void k_apgd_step(float* x_adv, float* x_old, float* x_best, float* x_best_adv, float* grad_best, const float* x0,
                  const float* grad, const uint32_t* flags, const float* step, int B, int64_t n_img, float eps,
                  const ApgdSched* sched, int32_t* ctr, int N, float a, int last, hipStream_t s, int* err = nullptr);
+// ---- Square attack (score-based random search, L-inf): elementwise.hip ----
+// Replay j of the captured iteration evaluates proposal j (replay 0: the stripes) and draws proposal j + 1.
+enum { SQ_PREV = 1u, SQ_ACCEPT = 2u, SQ_NEXT = 4u };      // per-image flag word of one replay: a pending window to resolve
+                                                          // (accepted or not), a next window to write
+struct SquareSched {    // the at most ten distinct sides of a schedule: proposal j >= from[i] uses side[i] (from[0] = 1)
+    int32_t from[10];
+    int32_t side[10];
+};
+struct SquareParams {   // what would otherwise be kernel arguments baked into the captured iteration
+    uint64_t key;       // seed * 0xD1342543DE82EF95
+    uint64_t offset;    // global index of image 0
+};
+struct SquareState {    // counter, table, per-image scalars and the trace rows, all inside the caller's scratch
+    int32_t* ctr;       // [4]: ctr[0] read by the track kernel, ctr[1] by the step kernel
+    SquareParams* par;
+    int32_t* side;      // [N + 1]: side[j] of proposal j (entry 0 unused)
+    float* margin_min;  // [B]
+    int32_t *queries, *robust;     // [B]
+    uint32_t* flags;    // [B]
+    int32_t *win_prev, *win_next;  // [B][4]: h, w, s, sign bits (bit c = channel c is +eps)
+    float* tr_margin;   // [N + 1][B]: the margin seen at replay j
+    int32_t* tr_win;    // [N][B][4]: h, w, s, signs | active << 3 | accepted << 4 of proposal j + 1 (all zero: no proposal)
+};
+void square_schedule(int S, int N, float p_init, SquareSched* out);      // host, in double
+void k_square_sched(const SquareState& st, const SquareSched& sc, int N, uint64_t seed, uint64_t image_offset, hipStream_t s);
+void k_square_init(float* x_cur, float* x_best, const float* x0, const SquareParams* par, int B, int S, float eps, hipStream_t s);
+// err (optional): set to 1 for a label outside [0, C), to 5 for a margin that is not finite
+void k_square_track(const SquareState& st, const float* logits, const int64_t* labels, int B, int C, int S, int N, hipStream_t s,
+                    int* err = nullptr);
+// ctr != nullptr: ctr[0] = ctr[1], nothing past replay N (the attack); nullptr: one launch on caller-owned buffers (vl_square_step)
+void k_square_step(float* x_cur, float* x_best, const float* x0, const uint32_t* flags, const int32_t* win_prev,
+                   const int32_t* win_next, int B, int S, float eps, int32_t* ctr, int N, hipStream_t s);
 // err (optional): set to 3 when a gradient element is not finite (that element is skipped)
 void k_adam(float* p, const float* g, float* m, float* v, float lr, float b1, float b2, float eps, int t, int64_t n,
             hipStream_t s, int* err = nullptr);

@@ -101,6 +101,7 @@ struct GraphEntry {
     hipGraphExec_t exec1;     // chains == 2: the second half-batch's iteration (launched on the side stream)
     // kind 1 = the APGD iteration (vl_apgd_attack): its kernels read the caller's scratch, so the key also holds that pointer,
     // the schedule length and rho (alpha is unused)
+    // kind 2 = the Square replay (vl_square_attack): keyed by batch, eps, the schedule length and the scratch pointer
     int kind = 0, steps = 0;
     const void* scratch = nullptr;
     float rho = 0.f;
@@ -157,6 +158,7 @@ struct vl_model {
     int fuse_down_min_k = 2048;   // LoRA down projection inside the ping-pong GEMM for projections at least this deep (VITLORA_FUSE_DOWN_MIN_K)
     int small_m_rows = 16384;     // token rows up to which the "small batch" forms apply (VITLORA_SMALL_M_ROWS; batch <= 83 at T = 197)
     int fuse_pgd = 1;         // vl_pgd_attack: PGD step inside the patch-gradient epilogue (VITLORA_FUSE_PGD=0: separate K10 launch)
+    int square_bare = 0;      // "square_bare" = 1: the Square replay is the forward alone (timing baseline of tools/square_bench.py)
     int* err_flag = nullptr;                    // pinned host word written by kernels (bad label, ...), read at API entry
     float mean[3] = {0.485f, 0.456f, 0.406f};   // get_normalization, Utils.py:92-93
     float stdv[3] = {0.229f, 0.224f, 0.225f};

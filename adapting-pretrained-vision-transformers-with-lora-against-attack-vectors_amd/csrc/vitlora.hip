@@ -239,6 +239,8 @@ int check_async(vl_model* m) {
                                    "skipped): drop that step or redo it with precision = f32");
         if (code == 4) return fail(VL_ERR_NONFINITE, "an earlier FORWARD pass left the fp16 range (the 16-bit residual stream exceeded 65504): "
                                    "redo that batch with precision = f32 or bf16");
+        if (code == 5) return fail(VL_ERR_NONFINITE, "an earlier vl_square_attack saw a margin that was not finite (the logits left the "
+                                   "number range): that query was not accepted; redo the batch with precision = f32 or bf16");
         return fail(VL_ERR_HIP, "device-side error flag %d", code);
     }
     return VL_OK;
@@ -1413,6 +1415,166 @@ int vl_apgd_step(float* x_adv, float* x_old, float* x_best, float* x_best_adv, f
 }
 #endif
 
+// ---- Square attack (L-inf, margin loss; include/vitlora.h) ----------------
+// Everything the attack keeps between replays, carved from the caller's scratch (base == nullptr: size only).
+struct SquareLayout {
+    float *x0, *x_cur, *x_best;
+    int64_t* labels;
+    SquareState st;
+};
+static size_t square_carve(const vl_model* m, int B, int N, char* base, SquareLayout& L) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) -> char* {
+        char* p = base ? base + off : nullptr;
+        off += (size_t)round_up((int64_t)bytes, 256);
+        return p;
+    };
+    const size_t img = (size_t)B * 3 * m->S * m->S * 4, row = (size_t)B * 4;
+    L.x0 = (float*)take(img); L.x_cur = (float*)take(img); L.x_best = (float*)take(img);
+    L.labels = (int64_t*)take((size_t)B * 8);
+    L.st.ctr = (int32_t*)take(16);
+    L.st.par = (SquareParams*)take(sizeof(SquareParams));
+    L.st.side = (int32_t*)take((size_t)(N + 1) * 4);
+    L.st.margin_min = (float*)take(row); L.st.queries = (int32_t*)take(row); L.st.robust = (int32_t*)take(row);
+    L.st.flags = (uint32_t*)take(row);
+    L.st.win_prev = (int32_t*)take(4 * row); L.st.win_next = (int32_t*)take(4 * row);
+    L.st.tr_margin = (float*)take((size_t)(N + 1) * row);
+    L.st.tr_win = (int32_t*)take((size_t)N * 4 * row);
+    return off;
+}
+static int square_check_scratch(const vl_model* m, const void* scratch, size_t bytes, int batch, int n_queries) {
+    if (m->C < 2) return fail(VL_ERR_UNSUPPORTED, "the margin loss needs num_labels >= 2");
+    if (!m->main.ws.max_batch) return fail(VL_ERR_STATE, "no workspace");
+    if (batch <= 0 || batch > m->main.ws.max_batch) return fail(VL_ERR_STATE, "batch exceeds planned workspace");
+    if (batch > 65535) return fail(VL_ERR_UNSUPPORTED, "Square runs at most 65535 images per call (one grid row per image)");
+    if (n_queries < 1 || n_queries > 65535) return fail(VL_ERR_ARG, "n_queries must be 1 .. 65535");
+    if (!scratch || ((uintptr_t)scratch & 255)) return fail(VL_ERR_ARG, "scratch must be a 256-byte aligned device buffer");
+    SquareLayout sz;
+    const size_t need = square_carve(m, batch, n_queries, nullptr, sz);
+    if (bytes < need) return fail(VL_ERR_ARG, "Square scratch too small: %zu < %zu (vl_square_scratch_bytes)", bytes, need);
+    return VL_OK;
+}
+
+int vl_square_scratch_bytes(vl_model* m, int batch, int n_queries, size_t* bytes) {
+    if (!m || !bytes || batch <= 0 || n_queries < 1 || n_queries > 65535) return fail(VL_ERR_ARG, "bad argument");
+    SquareLayout sz;
+    *bytes = square_carve(m, batch, n_queries, nullptr, sz);
+    return VL_OK;
+}
+
+// one replay in the main pass: evaluate x_cur (eval-mode forward, the last layer on the CLS rows alone), then the bookkeeping and
+// the pixels of the two windows
+static int square_iteration(vl_model* m, const SquareLayout& L, int B, int N, float eps, hipStream_t s) {
+    Pass& p = m->main;
+    const int rc = forward_impl(m, p, L.x_cur, B, 1, 0, s);
+    if (rc) return rc;
+    if (m->square_bare) return VL_OK;
+    k_square_track(L.st, p.ws.logits, L.labels, B, m->C, m->S, N, s, m->err_flag);
+    k_square_step(L.x_cur, L.x_best, L.x0, L.st.flags, L.st.win_prev, L.st.win_next, B, m->S, eps, L.st.ctr, N, s);
+    return VL_OK;
+}
+
+int vl_square_attack(vl_model* m, const vl_square_args* a) {
+    if (!m || !a) return fail(VL_ERR_ARG, "bad argument");
+    if (a->first < 0 || a->count < 1) return fail(VL_ERR_ARG, "first must be >= 0 and count >= 1");
+    if (a->first == 0 && (!a->x0 || !a->labels)) return fail(VL_ERR_ARG, "x0 and labels are needed when first == 0");
+    if (!(a->eps >= 0.f) || !(a->eps < INFINITY) || !(a->p_init > 0.f) || !(a->p_init <= 1.f))
+        return fail(VL_ERR_ARG, "eps must be finite and >= 0, p_init in (0, 1]");
+    int rc = square_check_scratch(m, a->scratch, a->scratch_bytes, a->batch, a->n_queries);
+    if (rc) return rc;
+    if ((int64_t)a->first + a->count > (int64_t)a->n_queries + 1) return fail(VL_ERR_ARG, "first + count exceeds the n_queries + 1 replays of the schedule");
+    hipStream_t s = (hipStream_t)a->stream;
+    if ((rc = check_async(m))) return rc;
+    if (m->dirty && (rc = vl_lora_commit(m, a->stream))) return rc;     // the attack sees the CURRENT adapters
+    const int B = a->batch, N = a->n_queries;
+    const float eps = a->eps;
+    SquareLayout L;
+    square_carve(m, B, N, (char*)a->scratch, L);
+    const int64_t n = (int64_t)B * 3 * m->S * m->S;
+    if (a->first == 0) {
+        // staging, as vl_pgd_attack: the captured iteration only ever sees addresses inside the scratch and the workspace
+        HIPCHK(hipMemcpyAsync(L.x0, a->x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(L.labels, a->labels, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        SquareSched sc;
+        square_schedule(m->S, N, a->p_init, &sc);
+        k_square_sched(L.st, sc, N, a->seed, a->image_offset, s);
+        k_square_init(L.x_cur, L.x_best, L.x0, L.st.par, B, m->S, eps, s);
+    }
+    m->fwd_chains = 0;
+    if (!m->use_graph || g_prof || g_poison_lds) {
+        for (int j = 0; j < a->count; ++j)
+            if ((rc = square_iteration(m, L, B, N, eps, s))) return rc;
+        if ((rc = check_launch("vl_square_attack"))) return rc;
+    } else {
+        hipGraphExec_t exec = nullptr;
+        for (GraphEntry& g : m->graphs)
+            if (g.kind == 2 && g.B == B && g.eps == eps && g.steps == N && g.scratch == a->scratch) { exec = g.exec; break; }
+        if (!exec) {      // captured cold on the private stream, as the PGD iteration
+            if (!m->cap_stream) HIPCHK(hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking));
+            hipGraph_t graph = nullptr;
+            (void)hipGetLastError();
+            HIPCHK(hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeThreadLocal));
+            const int rcc = square_iteration(m, L, B, N, eps, m->cap_stream);
+            hipError_t e = hipStreamEndCapture(m->cap_stream, &graph);
+            if (rcc) { if (graph) (void)hipGraphDestroy(graph); return rcc; }
+            if (e != hipSuccess) return fail(VL_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
+            dump_graph(graph);
+            e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+            (void)hipGraphDestroy(graph);
+            if (e != hipSuccess) return fail(VL_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
+            GraphEntry ge = {B, eps, 0.f, exec, 1, nullptr};
+            ge.kind = 2; ge.steps = N; ge.scratch = a->scratch;
+            remember_graph(m, ge);
+        }
+        for (int j = 0; j < a->count; ++j) HIPCHK(hipGraphLaunch(exec, s));
+    }
+    const size_t row = (size_t)B * 4;
+    const int done = a->first + a->count;          // replays 0 .. done - 1 have run
+    if (a->x_best) HIPCHK(hipMemcpyAsync(a->x_best, L.x_best, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (a->margin_min) HIPCHK(hipMemcpyAsync(a->margin_min, L.st.margin_min, row, hipMemcpyDeviceToDevice, s));
+    if (a->queries) HIPCHK(hipMemcpyAsync(a->queries, L.st.queries, row, hipMemcpyDeviceToDevice, s));
+    if (a->robust) HIPCHK(hipMemcpyAsync(a->robust, L.st.robust, row, hipMemcpyDeviceToDevice, s));
+    if (a->trace_margin) HIPCHK(hipMemcpyAsync(a->trace_margin, L.st.tr_margin, (size_t)done * row, hipMemcpyDeviceToDevice, s));
+    if (a->trace_win) HIPCHK(hipMemcpyAsync(a->trace_win, L.st.tr_win, (size_t)std::min(done, N) * 4 * row, hipMemcpyDeviceToDevice, s));
+    return VL_OK;
+}
+
+int vl_debug_square_track(vl_model* m, const vl_square_track_case* c, void* stream) {
+    if (!m || !c || !c->logits || !c->labels) return fail(VL_ERR_ARG, "bad argument");
+    if (c->reset && (!(c->p_init > 0.f) || !(c->p_init <= 1.f))) return fail(VL_ERR_ARG, "p_init in (0, 1]");
+    int rc = square_check_scratch(m, c->scratch, c->scratch_bytes, c->batch, c->n_queries);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    SquareLayout L;
+    square_carve(m, c->batch, c->n_queries, (char*)c->scratch, L);
+    if (c->reset) {
+        SquareSched sc;
+        square_schedule(m->S, c->n_queries, c->p_init, &sc);
+        k_square_sched(L.st, sc, c->n_queries, c->seed, c->image_offset, s);
+    }
+    k_square_track(L.st, c->logits, c->labels, c->batch, m->C, m->S, c->n_queries, s, nullptr);
+    HIPCHK(hipMemcpyAsync(L.st.ctr, L.st.ctr + 1, 4, hipMemcpyDeviceToDevice, s));      // what the step kernel does in the attack
+    const size_t row = (size_t)c->batch * 4;
+    if (c->flags_out) HIPCHK(hipMemcpyAsync(c->flags_out, L.st.flags, row, hipMemcpyDeviceToDevice, s));
+    if (c->win_prev_out) HIPCHK(hipMemcpyAsync(c->win_prev_out, L.st.win_prev, 4 * row, hipMemcpyDeviceToDevice, s));
+    if (c->win_next_out) HIPCHK(hipMemcpyAsync(c->win_next_out, L.st.win_next, 4 * row, hipMemcpyDeviceToDevice, s));
+    if (c->margin_min_out) HIPCHK(hipMemcpyAsync(c->margin_min_out, L.st.margin_min, row, hipMemcpyDeviceToDevice, s));
+    if (c->queries_out) HIPCHK(hipMemcpyAsync(c->queries_out, L.st.queries, row, hipMemcpyDeviceToDevice, s));
+    return VL_OK;
+}
+
+#ifndef VL_BF16
+int vl_square_step(float* x_cur, float* x_best, const float* x0, const uint32_t* flags, const int32_t* win_prev,
+                   const int32_t* win_next, int batch, int image_size, float eps, void* stream) {
+    if (!x_cur || !x_best || !x0 || !flags || !win_prev || !win_next || batch <= 0 || batch > 65535 || image_size <= 0 ||
+        image_size > 8192)
+        return fail(VL_ERR_ARG, "bad argument (batch 1 .. 65535, image_size 1 .. 8192)");
+    if (!(eps >= 0.f) || !(eps < INFINITY)) return fail(VL_ERR_ARG, "eps must be finite and >= 0");
+    k_square_step(x_cur, x_best, x0, flags, win_prev, win_next, batch, image_size, eps, nullptr, 0, (hipStream_t)stream);
+    return VL_OK;
+}
+#endif
+
 #ifndef VL_BF16
 int vl_adam_step(float* param, const float* grad, float* m1, float* m2, float lr, float b1, float b2, float eps, int t,
                  int64_t n, void* stream) {
@@ -1793,6 +1955,8 @@ int vl_debug_set_cus(vl_model* m, int cus) {
 //               captured iteration; 1: one chain always; 2: two chains whenever the chain workspaces hold the halves
 //   "api_chains" 0 (default); 1: vl_forward(train = 0) and the backward after it run batches of 2 .. 191 images as the same two
 //               chains (the adversarial-patch EoT step uses these calls); vl_debug_tensor then does not see the activations
+//   "square_bare" 0 (default); 1: a replay of vl_square_attack is the eval forward ALONE, captured and replayed the same way -- the
+//               baseline tools/square_bench.py measures a query against; the attack's results are then meaningless
 //   "poison_lds" 0 (default); 1: every profiled launch is preceded by a kernel that fills every CU's LDS with NaN patterns (test hook)
 int vl_debug_set_option(vl_model* m, const char* name, int value) {
     if (!m || !name) return fail(VL_ERR_ARG, "null argument");
@@ -1801,6 +1965,7 @@ int vl_debug_set_option(vl_model* m, const char* name, int value) {
     else if (!strcmp(name, "resid_epi")) m->resid_epi = value < 0 ? 0 : value > 2 ? 2 : value;
     else if (!strcmp(name, "attn_ring")) attention32_set_ring(value);        // process-wide
     else if (!strcmp(name, "poison_lds")) g_poison_lds = value ? 1 : 0;      // process-wide test hook (prof.h); attacks then run eagerly
+    else if (!strcmp(name, "square_bare")) m->square_bare = value ? 1 : 0;
     else if (!strcmp(name, "pgd_chains")) m->pgd_chains = value < 0 ? 0 : value > 2 ? 2 : value;    // 1: set BEFORE vl_plan to save the chain workspaces
     else if (!strcmp(name, "api_chains")) m->api_chains = value ? 1 : 0;      // vl_forward(train = 0) / vl_backward_input as two half-batch chains (2 .. 191 images)
     else return fail(VL_ERR_ARG, "unknown option %s", name);

@@ -374,6 +374,99 @@ class Engine:
         check(self.lib.vl_debug_apgd_track(self.h, C.byref(c), self._stream()), "vl_debug_apgd_track")
         return step, flags, best, robust
 
+    # -- Square attack (score-based random search, L-inf) ---------------------------------------------
+    def square_scratch_bytes(self, batch: int, n_queries: int) -> int:
+        n = C.c_size_t()
+        check(self.lib.vl_square_scratch_bytes(self.h, int(batch), int(n_queries), C.byref(n)), "vl_square_scratch_bytes")
+        return n.value
+
+    def _square_scratch(self, batch: int, n_queries: int):
+        """The attack's state (three image batches and the trace) as one tensor cached per (batch, n_queries): the same address
+        on every call, so the captured iteration is reused."""
+        cache = self.__dict__.setdefault("_square_scratch_cache", {})
+        key = (int(batch), int(n_queries))
+        if key not in cache:
+            while len(cache) >= 2:                 # a full batch and a ragged last one
+                cache.pop(next(iter(cache)))
+            n = self.square_scratch_bytes(batch, n_queries)
+            buf = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
+            cache[key] = (buf, (buf.data_ptr() + 255) // 256 * 256, n)
+        else:
+            cache[key] = cache.pop(key)            # most recently used last
+        return cache[key]
+
+    def square_attack(self, x0: torch.Tensor, labels: torch.Tensor, eps, n_queries=5000, p_init=0.8, seed=0, image_offset=0,
+                      check_every=0, trace=False, scratch=None, first=0, count=None) -> Dict[str, torch.Tensor]:
+        """vl_square_attack.  Returns {"x_best", "margin_min" [B], "queries" [B] int32, "robust" [B] bool, "replays": how many
+        replays of the n_queries + 1 have run} and with trace=True also {"trace_margin" [n_queries+1, B], "trace_win"
+        [n_queries, B, 4] int32}; rows of replays that did not run are zero.
+        check_every = K > 0: chunks of K replays, one look at `robust` (a synchronisation) after each, and no further chunk once
+        no image is active.  first / count: one chunk of the resumable call by hand (first > 0 continues the state the scratch
+        holds; check_every is ignored).  scratch: (base pointer, bytes) of a caller-owned buffer instead of the cached one."""
+        x0 = self._check_images(x0)
+        labels = labels.to(device=self.device, dtype=torch.int64).contiguous()
+        B, N = x0.shape[0], int(n_queries)
+        self.plan(B, False)
+        if scratch is None:
+            _, base, nbytes = self._square_scratch(B, N)
+        else:
+            base, nbytes = scratch
+        out = {"x_best": torch.empty_like(x0), "margin_min": torch.empty(B, dtype=torch.float32, device=self.device),
+               "queries": torch.empty(B, dtype=torch.int32, device=self.device),
+               "robust": torch.empty(B, dtype=torch.int32, device=self.device)}
+        if trace:
+            out["trace_margin"] = torch.zeros(N + 1, B, dtype=torch.float32, device=self.device)
+            out["trace_win"] = torch.zeros(N, B, 4, dtype=torch.int32, device=self.device)
+        a = _lib.VLSquareArgs()
+        a.x0, a.labels, a.batch, a.n_queries = x0.data_ptr(), labels.data_ptr(), B, N
+        a.eps, a.p_init = float(eps), float(p_init)
+        a.seed, a.image_offset = int(seed) & (2 ** 64 - 1), int(image_offset) & (2 ** 64 - 1)
+        a.scratch, a.scratch_bytes = base, nbytes
+        for k, t in out.items():
+            setattr(a, k, t.data_ptr())
+        a.stream = self._stream().value
+        self._keep, self._keep_labels = x0, labels
+        if count is not None or first:
+            chunks = [(int(first), int(count) if count is not None else N + 1 - int(first))]
+        elif check_every and int(check_every) > 0:
+            k = int(check_every)
+            chunks = [(lo, min(k, N + 1 - lo)) for lo in range(0, N + 1, k)]
+        else:
+            chunks = [(0, N + 1)]
+        done = 0
+        for i, (lo, cnt) in enumerate(chunks):
+            a.first, a.count = lo, cnt
+            check(self.lib.vl_square_attack(self.h, C.byref(a)), "vl_square_attack")
+            done = lo + cnt
+            if len(chunks) > 1 and i + 1 < len(chunks) and not bool((out["robust"] != 0).any()):
+                break
+        out["robust"] = out["robust"] != 0
+        out["replays"] = done
+        return out
+
+    def square_step(self, x_cur, x_best, x0, flags, win_prev, win_next, eps):
+        """vl_square_step on caller tensors: [B, 3, S, S] fp32 images (x_cur, x_best updated in place), flags [B] int32,
+        win_prev / win_next [B, 4] int32."""
+        B, S = x_cur.shape[0], x_cur.shape[-1]
+        check(self.lib.vl_square_step(*[C.c_void_p(t.data_ptr()) for t in (x_cur, x_best, x0, flags, win_prev, win_next)],
+                                      B, S, float(eps), self._stream()), "vl_square_step")
+
+    def square_track(self, scratch, batch, n_queries, logits, labels, p_init=0.8, seed=0, image_offset=0, reset=False):
+        """vl_debug_square_track: one call of the bookkeeping kernel on `scratch` = (base pointer, bytes); returns
+        {"flags" [B] int32, "win_prev" [B, 4], "win_next" [B, 4], "margin_min" [B], "queries" [B]} as left by that call."""
+        c = _lib.VLSquareTrackCase()
+        c.scratch, c.scratch_bytes = scratch
+        c.batch, c.n_queries, c.reset, c.p_init = int(batch), int(n_queries), int(bool(reset)), float(p_init)
+        c.seed, c.image_offset = int(seed) & (2 ** 64 - 1), int(image_offset) & (2 ** 64 - 1)
+        c.logits, c.labels = logits.data_ptr(), labels.data_ptr()
+        i32 = dict(dtype=torch.int32, device=self.device)
+        out = {"flags": torch.empty(batch, **i32), "win_prev": torch.empty(batch, 4, **i32), "win_next": torch.empty(batch, 4, **i32),
+               "margin_min": torch.empty(batch, dtype=torch.float32, device=self.device), "queries": torch.empty(batch, **i32)}
+        for k, t in out.items():
+            setattr(c, k + "_out", t.data_ptr())
+        check(self.lib.vl_debug_square_track(self.h, C.byref(c), self._stream()), "vl_debug_square_track")
+        return out
+
     def channel_affine(self, x: torch.Tensor, scale, shift, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         x = self._check_images(x)
         out = torch.empty_like(x) if out is None else out

@@ -2,15 +2,20 @@
 """AutoAttack's "auto" split on MI355X -- command-line compatible with the reference's auto_attack.py (flags: auto_attack.py:12-21;
 directory layout <out>/<model>/<source>/<split>/auto/images/*.png + auto/metadata.csv: :60-68,112-115).
 
-The reference runs AutoAttack(norm='Linf', eps, version='standard', seed=42) on every batch (:98-108).  Of that suite only its
-first component, APGD-CE, is built here (vl_apgd_attack: the whole Auto-PGD loop on the device), so this script runs
-AutoAttack(version='custom', attacks_to_run=['apgd-ce']): an image that is classified correctly and that APGD-CE fools is
-replaced by the misclassified point, every other image is written as it was.  APGD-T, FAB-T and Square are not built.
+The reference runs AutoAttack(norm='Linf', eps, version='standard', seed=42) on every batch (:98-108).  Of that suite the first
+component, APGD-CE (vl_apgd_attack: the whole Auto-PGD loop on the device), and the last, Square (vl_square_attack: score-based
+random search on the logits, no gradient), are built.  By default this script runs AutoAttack(version='custom',
+attacks_to_run=['apgd-ce']): an image that is classified correctly and that APGD-CE fools is replaced by the misclassified point,
+every other image is written as it was.  --attacks apgd-ce square adds Square for the images APGD-CE leaves robust -- the
+gradient-free cross-check of an adapter that may only be masking its gradients.  APGD-T and FAB-T are not built.
 Extensions, all opt-in:
   --synthetic N           no dataset / checkpoint on disk: N seeded random images per split and seeded random-init weights.
   --arch tiny|vit_b|vit_l architecture of the checkpoint (default vit_b = google/vit-base-patch16-224).
   --precision f16|bf16|f32
   --steps K               APGD iterations (the package's standard version uses 100).
+  --attacks A [A ...]     components to run in order, from apgd-ce and square (default: apgd-ce).
+  --square_queries N      Square's query budget (the package's standard version uses 5000).
+  --check_every K         Square looks at the robust flags every K queries and stops once every image is fooled (0 = never look).
 """
 import argparse
 import importlib
@@ -25,7 +30,7 @@ V = importlib.import_module("adapting-pretrained-vision-transformers-with-lora-a
 
 
 def build_parser():
-    p = argparse.ArgumentParser(description="Generate AutoAttack (APGD-CE; MI355X / HIP)")
+    p = argparse.ArgumentParser(description="Generate AutoAttack (APGD-CE, Square; MI355X / HIP)")
     p.add_argument("--data_root", required=False, default=None)
     p.add_argument("--model", required=True, help="Model architecture name of the output tree (e.g., google_vit)")
     p.add_argument("--source", required=True, help="Source dataset (e.g., gtsrb)")
@@ -40,6 +45,9 @@ def build_parser():
     p.add_argument("--precision", choices=["f16", "bf16", "f32"], default="f16")
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--seed", type=int, default=42)
+    p.add_argument("--attacks", nargs="+", choices=["apgd-ce", "square"], default=["apgd-ce"])
+    p.add_argument("--square_queries", type=int, default=5000)
+    p.add_argument("--check_every", type=int, default=0)
     return p
 
 
@@ -96,19 +104,26 @@ def main(argv=None):
         seen, n_robust = [], 0
         for images, labels, filenames in batches(args, split, class_to_idx, model):
             images, labels = images.to(device), labels.to(device)
+            offset = len(seen)                # Square draws by the image's index in the split, not by its place in the batch
             seen.extend(filenames)
-            adversary = V.AutoAttack(model, norm="Linf", eps=args.epsilon, version="custom", attacks_to_run=["apgd-ce"],
-                                     seed=args.seed, steps=args.steps, mean=mean, std=std)
-            x_adv = adversary.run_standard_evaluation(images, labels, bs=args.batch_size)
+            adversary = V.AutoAttack(model, norm="Linf", eps=args.epsilon, version="custom", attacks_to_run=args.attacks,
+                                     seed=args.seed, steps=args.steps, mean=mean, std=std, square_queries=args.square_queries,
+                                     check_every=args.check_every)
+            x_adv = adversary.run_standard_evaluation(images, labels, bs=args.batch_size, image_offset=offset)
             engine.check()                   # synchronises; fp16 mode: raises if a gradient left the fp16 range
             n_robust += round(adversary.robust_accuracy * len(filenames))
             iomod.save_images(x_adv, filenames, output_dir, engine=engine)
-        print(f"  robust accuracy under APGD-CE (eps {args.epsilon:g}, {args.steps} steps): {n_robust}/{len(seen)}")
+        if args.attacks == ["apgd-ce"]:
+            print(f"  robust accuracy under APGD-CE (eps {args.epsilon:g}, {args.steps} steps): {n_robust}/{len(seen)}")
+        else:
+            budget = {"apgd-ce": f"{args.steps} steps", "square": f"{args.square_queries} queries"}
+            print(f"  robust accuracy under {' + '.join(args.attacks)} (eps {args.epsilon:g}, "
+                  f"{', '.join(budget[a] for a in args.attacks)}): {n_robust}/{len(seen)}")
         if not args.synthetic:
             clean_meta = os.path.join(args.data_root, split, "metadata.csv")
             meta = iomod.create_adv_metadata(clean_meta, seen, output_dir)
             meta.to_csv(os.path.join(output_dir, "..", "metadata.csv"), index=False)
-        print(f"AutoAttack (APGD-CE) results saved to: {os.path.dirname(output_dir)}")
+        print(f"AutoAttack ({' + '.join(a.upper() for a in args.attacks)}) results saved to: {os.path.dirname(output_dir)}")
 
 
 if __name__ == "__main__":

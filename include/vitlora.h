@@ -254,6 +254,86 @@ typedef struct vl_apgd_track_case {
 } vl_apgd_track_case;
 int vl_debug_apgd_track(vl_model* m, const vl_apgd_track_case* c, void* stream);
 
+/* ---- Square attack, L-inf (Andriushchenko et al. 2020): the LAST component of AutoAttack(model, norm='Linf', eps,
+ * version='standard'), which auto_attack.py:98-108 runs -- a score-based random search that reads only the logits, the suite's
+ * gradient-free cross-check.  The algorithm is the restatement in DESIGN.md section 3.10 and tests/square_ref.py, written from
+ * memory of the autoattack package's square.py and the paper (neither installed here): PARITY WITH THE PACKAGE IS UNPINNED.
+ * Two DELIBERATE DEVIATIONS from the package: the window and its signs are drawn PER IMAGE from a counter-based generator keyed
+ * by the image's global index image_offset + b (the package draws one window per batch; here an image's random stream depends
+ * neither on its neighbours nor on how a dataset is cut into batches), and the window is written as clamp(x0 +- eps, 0, 1)
+ * directly (the package adds 2 eps to the best point and projects).
+ * Loss: the untargeted margin m = z_y - max_{j != y} z_j on the fp32 logits.  Schedule: proposal j = 1 .. n_queries has the
+ * side s_j = min(S, max(1, round_half_even(sqrt(p S S)))), p = p_init / 2^k, k = how many of {10, 50, 200, 500, 1000, 2000,
+ * 4000, 6000, 8000} the value int((j - 1) / n_queries * 10000) exceeds.  Replay 0 evaluates the start point (vertical stripes
+ * x0 +- eps, one sign per image, channel and column); replay j evaluates proposal j: x_best with one s_j x s_j window, at a
+ * uniform position, set to x0 + eps or x0 - eps per channel; it is accepted iff its margin is below margin_min.  An image with
+ * margin_min <= 0 is frozen: no proposal, no query counted, x_best final; it is still forwarded (the batch shape is fixed).
+ * A margin that is not finite is never accepted and makes a LATER call return VL_ERR_NONFINITE.
+ * One iteration (eval-mode forward of x_cur with normalised pixels, square_track_kernel, square_step_kernel) is captured once
+ * and replayed; the replay index is a device-side counter; the step kernel touches only the union of the previous and the next
+ * window.  No device-to-host copy, no stream synchronisation.  One chain only.
+ * RESUMABLE: a call runs replays first .. first + count - 1 of the n_queries + 1 the schedule has.  first == 0 stages x0 and
+ * labels, builds the schedule and initialises the state; first > 0 continues from the state `scratch` holds (x0, labels,
+ * p_init, seed and image_offset of THAT call are ignored; eps must be what it was) -- the caller guarantees that the scratch is untouched since the
+ * previous chunk and that first is where that chunk ended; this cannot be checked without a synchronisation.  The outputs are
+ * copied out after every call, so a caller may run a few hundred queries, look at `robust` and stop early.
+ * ALL state lives in `scratch` (vl_square_scratch_bytes; 256-byte aligned, the only memory besides the workspace that the call
+ * writes; results do not depend on what it held at first == 0): x0, x_cur, x_best (three image batches), labels, the counter,
+ * the side table, the per-image scalars and the trace.  vl_plan and the workspace are unchanged.
+ * Refused (nothing is launched): num_labels < 2, batch > 65535, n_queries outside 1 .. 65535, first < 0, count < 1,
+ * first + count > n_queries + 1, eps not finite or < 0, p_init outside (0, 1], an unaligned or too small scratch. */
+typedef struct vl_square_args {
+    const float* x0;          /* [B,3,S,S] fp32 in [0,1] (read when first == 0) */
+    const int64_t* labels;    /* [B] (read when first == 0) */
+    int32_t batch;
+    int32_t n_queries;        /* N >= 1: the forwards an active image gets besides the start point */
+    int32_t first;            /* first replay of this call, 0 .. N */
+    int32_t count;            /* replays of this call, >= 1 */
+    float eps;
+    float p_init;             /* .8 */
+    uint64_t seed;
+    uint64_t image_offset;    /* global index of image 0 of this batch */
+    void* scratch;
+    size_t scratch_bytes;
+    /* outputs, each may be NULL; the state after replay first + count - 1 */
+    float* x_best;            /* [B,3,S,S] */
+    float* margin_min;        /* [B] the margin at x_best */
+    int32_t* queries;         /* [B] forwards spent on this image while it was active (the start point included) */
+    int32_t* robust;          /* [B] margin_min > 0 */
+    /* optional trace; rows of replays that have not run yet are not written */
+    float* trace_margin;      /* [N + 1][B] the margin seen at replay j (a frozen image's rows equal its margin_min) */
+    int32_t* trace_win;       /* [N][B][4] row j - 1 = proposal j: h, w, s, signs | active << 3 | accepted << 4 (signs bit c: channel c
+                                 is +eps); all zero for an image that was frozen */
+    void* stream;
+    int32_t reserved[4];
+} vl_square_args;
+int vl_square_scratch_bytes(vl_model* m, int batch, int n_queries, size_t* bytes);
+int vl_square_attack(vl_model* m, const vl_square_args* args);
+
+/* One launch of square_step_kernel on CALLER-OWNED buffers (tests): [batch,3,S,S] fp32 images, per image b the flag word flags[b] =
+ * 1 a previous window to resolve | 2 it was accepted | 4 a next window, and the windows win_prev[b] / win_next[b] = {h, w, s,
+ * signs}.  Only pixels of the union of the two windows are touched, each by one thread, which does in order:
+ *   in the previous window:  accepted: x_best <- x_cur;  else: x_cur <- x_best;
+ *   in the next window:      x_cur <- clamp(x0 + eps, 0, 1) where bit c of signs is set for the pixel's channel c, else x0 - eps.
+ * A window that does not lie inside the image is ignored.  x0 is not written. */
+int vl_square_step(float* x_cur, float* x_best, const float* x0, const uint32_t* flags, const int32_t* win_prev,
+                   const int32_t* win_next, int batch, int image_size, float eps, void* stream);
+
+/* One launch of square_track_kernel (tests): the state lives in `scratch` as in vl_square_attack (sized for batch, n_queries).
+ * reset != 0 first builds the side table from p_init, stores seed / image_offset and zeroes the replay counter; each call then
+ * consumes one replay index (call j = replay j) from logits [B][num_labels] and labels [B] and copies out what the kernel left:
+ * flags_out [B], win_prev_out / win_next_out [B][4], margin_min_out [B], queries_out [B] (each may be NULL).  A margin that is
+ * not finite does not raise the error word here. */
+typedef struct vl_square_track_case {
+    void* scratch; size_t scratch_bytes;
+    int32_t batch, n_queries, reset, reserved0;
+    float p_init, reserved1;
+    uint64_t seed, image_offset;
+    const float* logits; const int64_t* labels;
+    uint32_t* flags_out; int32_t* win_prev_out; int32_t* win_next_out; float* margin_min_out; int32_t* queries_out;
+} vl_square_track_case;
+int vl_debug_square_track(vl_model* m, const vl_square_track_case* c, void* stream);
+
 /* optimizer.step() of torch.optim.Adam(lr, betas, eps) (train_loras.py:284,315) on a
  * flat buffer; t = 1-based step count. */
 int vl_adam_step(float* param, const float* grad, float* m1, float* m2, float lr, float b1,
@@ -374,7 +454,9 @@ int vl_debug_set_gemm_stream(int mode);
  * carved behind the main one by vl_plan, two streams that meet at the start and the end of the attack; 1: one chain always, set
  * BEFORE vl_plan to save those workspaces; 2: two chains whenever the halves fit) and "api_chains" (0, default; 1: vl_forward(train = 0)
  * and the backward after it run such batches as the same two chains -- the adversarial-patch EoT step goes through these calls;
- * vl_debug_tensor then does not see the activations).  Results are bit-identical either way. */
+ * vl_debug_tensor then does not see the activations).  Results are bit-identical either way.  "square_bare" (0, default; 1: a replay
+ * of vl_square_attack is the eval-mode forward alone, with no bookkeeping -- the baseline tools/square_bench.py times a query
+ * against; the attack's outputs are then meaningless). */
 int vl_debug_set_option(vl_model* m, const char* name, int value);
 int vl_debug_set_cus(vl_model* m, int cus);   /* grid size of the persistent GEMM kernels -- 256-row, ping-pong, streaming (diagnostic; default = the device's CU count) */
 
