@@ -15,7 +15,7 @@ stale() {   # stale <object> <source>
   for h in $HDRS; do [ "$h" -nt "$1" ] && return 0; done
   return 1
 }
-BOTH="gemm gemm256 gemm_pp gemm_stream elementwise attention32 cls_path lora_grad vitlora"
+BOTH="gemm gemm256 gemm_pp gemm_stream elementwise attention32 cls_path lora_grad vitlora vit_attacks"
 ONCE="f32_kernels patch swin vitlora_f32"
 pids=()
 njobs=0

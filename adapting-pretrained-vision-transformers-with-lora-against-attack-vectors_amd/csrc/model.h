@@ -1,5 +1,5 @@
-// Model handle, packed weights and workspace of libvitlora_hip.so, shared by the API file
-// (vitlora.hip: 16-bit operand path) and the fp32 parity path (vitlora_f32.hip).
+// Model handle, packed weights and workspace of libvitlora_hip.so, shared by the API files
+// (vitlora.hip: 16-bit operand path; vit_attacks.hip: the attacks) and the fp32 parity path (vitlora_f32.hip).
 #pragma once
 #include <cstddef>
 #include <string>
@@ -94,18 +94,33 @@ struct Pass {
     int norm = 0, train = 0, cls_only = 0, have_loss = 0;     // cls_only: that forward ran the last layer on the CLS rows only
 };
 
-struct GraphEntry {
-    int B; float eps, alpha;
-    hipGraphExec_t exec;
-    int chains;
-    hipGraphExec_t exec1;     // chains == 2: the second half-batch's iteration (launched on the side stream)
-    // kind 1 = the APGD iteration (vl_apgd_attack): its kernels read the caller's scratch, so the key also holds that pointer,
-    // the schedule length and rho (alpha is unused)
-    // kind 2 = the Square replay (vl_square_attack): keyed by batch, eps, the schedule length and the scratch pointer
-    int kind = 0, steps = 0;
-    const void* scratch = nullptr;
-    float rho = 0.f;
+// Cache of captured attack iterations (vit_attacks.hip).  The key is everything an iteration bakes in besides the handle's options
+// (a changed option drops the whole cache: drop_graphs); fields a kind does not use stay 0 / nullptr.  PGD: B, chains, eps, alpha
+// (its staging buffers live in the workspace).  APGD: B, steps, eps, rho and the caller's scratch, which its kernels read.
+// Square: B, steps (n_queries), eps, scratch.
+enum { GRAPH_PGD = 0, GRAPH_APGD = 1, GRAPH_SQUARE = 2 };
+struct GraphKey {
+    int kind, B, chains, steps; float eps, alpha, rho; const void* scratch;
+    bool operator==(const GraphKey& o) const {
+        return kind == o.kind && B == o.B && chains == o.chains && steps == o.steps && eps == o.eps && alpha == o.alpha && rho == o.rho &&
+               scratch == o.scratch;
+    }
 };
+struct GraphEntry { GraphKey key; hipGraphExec_t exec[2]; };   // exec[1]: the second half-batch chain's iteration (side stream), else nullptr
+
+// Hands out consecutive pieces of one buffer, each rounded up to 256 bytes.  base == nullptr: a size query -- every piece comes
+// out null and `off` still counts.
+struct Carver {
+    char* base; size_t off;
+    template <class T> T* take(size_t bytes) {
+        T* p = base ? (T*)(base + off) : nullptr;
+        off += (size_t)round_up((int64_t)bytes, 256);
+        return p;
+    }
+};
+
+// K10 fused into the patch-gradient epilogue: the pixel gradient never goes to HBM (vl_pgd_attack; vl_pgd_step stays the ABI entry)
+struct PgdFuse { float* adv; const float* x0; float eps, alpha; };
 
 }  // namespace VLNS
 
@@ -131,7 +146,7 @@ struct vl_model {
     int dirty = 1;                              // flat parameters changed since the last vl_lora_commit
     VLNS::Pass main;                            // the whole-batch pass: every API call without chains, the gathered logits / loss with them
     uint64_t drop_seed = 0x5eed, drop_base = 0x5eed, drop_calls = 0;   // LoRA dropout: seed of the last train-mode forward
-    // PGD graph cache (one executable graph per (batch, eps, alpha); staging buffers make it pointer-independent)
+    // the one cache of captured attack iterations (PGD, APGD, Square: GraphKey above), oldest first, at most 8 (vit_attacks.hip)
     std::vector<VLNS::GraphEntry> graphs;
     hipStream_t cap_stream = nullptr;
     // vl_pgd_attack at small batches (round 4): the batch runs as TWO independent half-batch chains, captured as parallel branches
@@ -175,17 +190,40 @@ int vl_fail(int code, const char* fmt, ...);
     } while (0)
 namespace VLNS {
 bool vl_drop_on(const vl_model* m, const Pass& p);      // LoRA dropout applies to the forward that pass `p` holds
+int check_async(vl_model* m);             // errors a kernel reported through the pinned host word, surfaced by the next API call
+int check_launch(const char* what);       // sticky launch failures, read after a launch sequence that ran OUTSIDE stream capture
+int chain_resources(vl_model* m);         // side stream and fork / join events of the two half-batch chains, created on first use
+// one forward of B images in pass `p`; on success p holds it (B, rows, norm, train, cls_only) and no loss yet
+int forward_impl(vl_model* m, Pass& p, const float* x, int B, int normalise, int train, hipStream_t s);
+// shared dgrad chain: flat_grad != null additionally produces the LoRA / classifier gradients, grad_x != null the input gradient,
+// pf != null applies the PGD step in the patch-gradient epilogue instead
+int backward_impl(vl_model* m, Pass& p, float* grad_x, float* flat_grad, hipStream_t s, const PgdFuse* pf = nullptr);
+
+// runs fn(c, half pass c, its stream) for both half passes -- chain 0 on `s`, chain 1 on the side stream -- between the fork and
+// the join event; returns the first failure
+template <typename F>
+int on_both_halves(vl_model* m, hipStream_t s, F fn) {
+    HIPCHK(hipEventRecord(m->ev_fork, s));
+    HIPCHK(hipStreamWaitEvent(m->side_stream, m->ev_fork, 0));
+    const int rc0 = fn(0, m->half[0], s), rc1 = fn(1, m->half[1], m->side_stream);
+    HIPCHK(hipEventRecord(m->ev_join, m->side_stream));
+    HIPCHK(hipStreamWaitEvent(s, m->ev_join, 0));
+    return rc0 ? rc0 : rc1;
+}
+
+// graph cache, defined in vit_attacks.hip
+void drop_graphs(vl_model* m);            // destroys every cached iteration (an option or the workspace changed; vl_destroy)
 
 // fp32 parity path (vitlora_f32.hip): reached through the fp16 build only (vl_create_bf16 refuses VL_PREC_F32)
 #ifdef VL_BF16
-static inline size_t f32_carve(const vl_model*, Workspace&, int, char*, size_t off0) { return off0; }
+static inline size_t f32_carve(const vl_model*, Workspace&, int, Carver& cv) { return cv.off; }
 static inline int f32_forward(vl_model*, Pass&, const float*, int, int, hipStream_t) { return VL_ERR_STATE; }
 static inline int f32_backward(vl_model*, Pass&, float*, float*, hipStream_t) { return VL_ERR_STATE; }
 static inline int f32_init(int) { return 0; }
 static inline int f32_debug_gemm(const vl_gemm_case*, hipStream_t) { return VL_ERR_STATE; }
 static inline int f32_debug_attention(const vl_attn_case*, hipStream_t) { return VL_ERR_STATE; }
 #else
-size_t f32_carve(const vl_model* m, Workspace& w, int train, char* base, size_t off0);      // w.Mpad / w.Mppad are set by the caller
+size_t f32_carve(const vl_model* m, Workspace& w, int train, Carver& cv);      // goes on from cv; w.Mpad / w.Mppad are set by the caller
 int f32_forward(vl_model* m, Pass& p, const float* x, int B, int normalise, hipStream_t s);  // p.train / p.rows are set by the caller
 int f32_backward(vl_model* m, Pass& p, float* grad_x, float* flat_grad, hipStream_t s);
 int f32_init(int device);     // kernel attributes; 0 = ok

@@ -1539,12 +1539,8 @@ int vl_swin_set_normalization(vl_swin* m, const float mean[3], const float stdv[
 // base == nullptr: a size query, `w` is a throw-away.
 static size_t swin_carve(const vl_swin* m, SwinWs& w, int B, char* base) {
     w.max_batch = base ? B : 0; w.cur_B = 0; w.have_loss = 0;
-    size_t off = 0;
-    auto take = [&](size_t bytes) -> float* {
-        char* p = base ? base + off : nullptr;
-        off += (size_t)round_up((int64_t)bytes, 256);
-        return (float*)p;
-    };
+    Carver cv{base, 0};
+    auto take = [&](size_t bytes) { return cv.take<float>(bytes); };
     const int L0 = m->G0 * m->G0, PK = 3 * m->P * m->P;
     const int64_t R0 = round_up((int64_t)B * L0, 64);
     w.patches = take((size_t)R0 * PK * 4);
@@ -1605,7 +1601,7 @@ static size_t swin_carve(const vl_swin* m, SwinWs& w, int B, char* base) {
     const size_t img = (size_t)B * 3 * m->S * m->S * 4;
     w.grad_img = take(img); w.stage_x0 = take(img); w.stage_adv = take(img);
     w.stage_labels = (int64_t*)take((size_t)B * 8);
-    return off;
+    return cv.off;
 }
 
 // chain workspaces: each for ceil(max_batch / 2) images, carved into the same bytes as the main workspace

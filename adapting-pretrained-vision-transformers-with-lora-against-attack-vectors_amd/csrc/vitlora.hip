@@ -1,7 +1,8 @@
 // C ABI of libvitlora_hip.so (include/vitlora.h): model handle, packed weights, workspace
-// plan and the launch sequences for forward, backward-to-input, LoRA backward and the PGD
-// loop (one hipGraph per iteration).  Host-side orchestration only: all arithmetic is in
-// gemm.hip / attention.hip / elementwise.hip / lora_grad.hip.
+// plan and the launch sequences for forward, backward-to-input and LoRA backward, plus the
+// debug and profiling entry points.  The attacks (PGD, APGD, Square) and their graph cache
+// are in vit_attacks.hip.  Host-side orchestration only: all arithmetic is in
+// gemm*.hip / attention32.hip / cls_path.hip / elementwise.hip / lora_grad.hip.
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
@@ -227,6 +228,22 @@ int parse_layer(const char* name, const char** rest) {
     return (int)i;
 }
 
+bool capturing(hipStream_t s) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return st != hipStreamCaptureStatusNone;
+}
+
+// the two switches read here that are neither a flag nor an integer (every other one goes through env.h)
+// VITLORA_RESID: "ln" = 0, "o" = 1, anything else or unset = 2 (vl_model::resid_epi)
+int env_resid() { const char* e = getenv("VITLORA_RESID"); return !e ? 2 : !strcmp(e, "ln") ? 0 : !strcmp(e, "o") ? 1 : 2; }
+// VITLORA_ATTN_IMG: unset = -1 (by batch size), a value starting with '1' = on, any other value = off
+int env_attn_img() { const char* e = getenv("VITLORA_ATTN_IMG"); return e ? (e[0] == '1' ? 1 : 0) : -1; }
+
+}  // namespace
+
+bool vl_drop_on(const vl_model* m, const Pass& p) { return p.train && m->r && m->cfg.lora_dropout > 0.f; }
+
 // errors a kernel reported through the pinned host word (label out of range): surfaced by the next API call
 int check_async(vl_model* m) {
     if (m->err_flag && *m->err_flag) {
@@ -254,35 +271,12 @@ int check_launch(const char* what) {
     return VL_OK;
 }
 
-bool capturing(hipStream_t s) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return st != hipStreamCaptureStatusNone;
+int chain_resources(vl_model* m) {
+    if (!m->side_stream) HIPCHK(hipStreamCreateWithFlags(&m->side_stream, hipStreamNonBlocking));
+    if (!m->ev_fork) HIPCHK(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
+    if (!m->ev_join) HIPCHK(hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming));
+    return VL_OK;
 }
-
-// runs fn(c, half pass c, its stream) for both half passes -- chain 0 on `s`, chain 1 on the side stream -- between the fork and
-// the join event; returns the first failure
-template <typename F>
-int on_both_halves(vl_model* m, hipStream_t s, F fn) {
-    HIPCHK(hipEventRecord(m->ev_fork, s));
-    HIPCHK(hipStreamWaitEvent(m->side_stream, m->ev_fork, 0));
-    const int rc0 = fn(0, m->half[0], s), rc1 = fn(1, m->half[1], m->side_stream);
-    HIPCHK(hipEventRecord(m->ev_join, m->side_stream));
-    HIPCHK(hipStreamWaitEvent(s, m->ev_join, 0));
-    return rc0 ? rc0 : rc1;
-}
-
-// the three switches that are neither a flag nor an integer (every other one goes through env.h)
-// VITLORA_RESID: "ln" = 0, "o" = 1, anything else or unset = 2 (vl_model::resid_epi)
-int env_resid() { const char* e = getenv("VITLORA_RESID"); return !e ? 2 : !strcmp(e, "ln") ? 0 : !strcmp(e, "o") ? 1 : 2; }
-// VITLORA_ATTN_IMG: unset = -1 (by batch size), a value starting with '1' = on, any other value = off
-int env_attn_img() { const char* e = getenv("VITLORA_ATTN_IMG"); return e ? (e[0] == '1' ? 1 : 0) : -1; }
-// VITLORA_GRAPH_DUMP: a file path, nullptr when unset or empty
-const char* env_graph_dump() { const char* e = getenv("VITLORA_GRAPH_DUMP"); return e && e[0] ? e : nullptr; }
-
-}  // namespace
-
-bool vl_drop_on(const vl_model* m, const Pass& p) { return p.train && m->r && m->cfg.lora_dropout > 0.f; }
 
 extern "C" {
 
@@ -411,7 +405,7 @@ int vl_create(const vl_config* cfg, vl_model** out) {
 
 int vl_destroy(vl_model* m) {
     if (!m) return VL_OK;
-    for (GraphEntry& g : m->graphs) { (void)hipGraphExecDestroy(g.exec); if (g.exec1) (void)hipGraphExecDestroy(g.exec1); }
+    drop_graphs(m);
     if (m->cap_stream) (void)hipStreamDestroy(m->cap_stream);
     if (m->side_stream) (void)hipStreamDestroy(m->side_stream);
     if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
@@ -586,106 +580,78 @@ int vl_merge_weight(vl_model* m, int layer, uint32_t target, const float* W_in, 
 static size_t carve(const vl_model* m, Workspace& w, int B, int train, char* base) {
     const int D = m->D, L = m->L, MLP = m->MLP;
     const int64_t Mpad = pad_rows(m, B), Mppad = pad_patch_rows(m, B);
-    size_t off = 0;
-    auto take = [&](size_t bytes) -> char* {
-        char* p = base ? base + off : nullptr;
-        off += (size_t)round_up((int64_t)bytes, 256);
-        return p;
-    };
+    Carver cv{base, 0};
     w.base = base; w.max_batch = base ? B : 0; w.train = train;
     w.Mpad = Mpad; w.Mppad = Mppad;
     // ---- common to both precisions: statistics, head, attack staging; the residual stream and its gradient stream are
     // fp32 in the fp32 parity mode and h16 on the 16-bit path (round 4: a LayerNorm pass moves 8 B per element, not 12 / 16) ----
     w.xs.assign(2 * L + 1, nullptr); w.xs16.assign(2 * L + 1, nullptr);
-    if (m->f32) for (auto& p : w.xs) p = (float*)take((size_t)Mpad * D * 4);
-    else for (auto& p : w.xs16) p = (h16*)take((size_t)Mpad * D * 2);
+    if (m->f32) for (auto& p : w.xs) p = cv.take<float>((size_t)Mpad * D * 4);
+    else for (auto& p : w.xs16) p = cv.take<h16>((size_t)Mpad * D * 2);
     w.mean.resize(2 * L); w.rstd.resize(2 * L);
-    for (int i = 0; i < 2 * L; ++i) { w.mean[i] = (float*)take(Mpad * 4); w.rstd[i] = (float*)take(Mpad * 4); }
+    for (int i = 0; i < 2 * L; ++i) { w.mean[i] = cv.take<float>(Mpad * 4); w.rstd[i] = cv.take<float>(Mpad * 4); }
     w.lse.resize(L);
-    for (int l = 0; l < L; ++l) w.lse[l] = (float*)take((size_t)B * m->H * m->T * 4);
-    w.xhat = (float*)take((size_t)B * D * 4); w.xf = (float*)take((size_t)B * D * 4);
-    w.rstd_f = (float*)take((size_t)B * 4);
-    w.logits = (float*)take((size_t)B * m->C * 4); w.dlogits = (float*)take((size_t)B * m->C * 4);
-    w.loss = (float*)take(256);
-    w.loss_img = (float*)take((size_t)B * 4);
-    w.gscale = (float*)take((size_t)B * 4); w.inv_gscale = (float*)take((size_t)B * 4);
+    for (int l = 0; l < L; ++l) w.lse[l] = cv.take<float>((size_t)B * m->H * m->T * 4);
+    w.xhat = cv.take<float>((size_t)B * D * 4); w.xf = cv.take<float>((size_t)B * D * 4);
+    w.rstd_f = cv.take<float>((size_t)B * 4);
+    w.logits = cv.take<float>((size_t)B * m->C * 4); w.dlogits = cv.take<float>((size_t)B * m->C * 4);
+    w.loss = cv.take<float>(256);
+    w.loss_img = cv.take<float>((size_t)B * 4);
+    w.gscale = cv.take<float>((size_t)B * 4); w.inv_gscale = cv.take<float>((size_t)B * 4);
     w.dres[0] = w.dres[1] = nullptr;
-    if (m->f32) { w.dres[0] = (float*)take((size_t)Mpad * D * 4); w.dres[1] = (float*)take((size_t)Mpad * D * 4); }
+    if (m->f32) { w.dres[0] = cv.take<float>((size_t)Mpad * D * 4); w.dres[1] = cv.take<float>((size_t)Mpad * D * 4); }
     const size_t img = (size_t)B * 3 * m->S * m->S * 4;
-    w.grad_img = (float*)take(img);
-    w.stage_x0 = (float*)take(img); w.stage_adv = (float*)take(img);
-    w.stage_labels = (int64_t*)take((size_t)B * 8);
-    if (m->f32) return w.bytes = f32_carve(m, w, train, base, off);
+    w.grad_img = cv.take<float>(img);
+    w.stage_x0 = cv.take<float>(img); w.stage_adv = cv.take<float>(img);
+    w.stage_labels = cv.take<int64_t>((size_t)B * 8);
+    if (m->f32) return w.bytes = f32_carve(m, w, train, cv);
     // ---- 16-bit operand path ----
-    w.patches = (h16*)take((size_t)Mppad * m->PK * 2);
+    w.patches = cv.take<h16>((size_t)Mppad * m->PK * 2);
     w.h1.resize(L); w.h2.resize(L); w.a.resize(L); w.qkv.resize(L); w.ctx.resize(L); w.z.resize(L);
     int kext_max = 64;
     for (int k = 0; k < 4; ++k) { w.t[k].resize(L); if (m->layers[0].lin[k].kext > kext_max) kext_max = m->layers[0].lin[k].kext; }
-    h16* sh_h = train ? nullptr : (h16*)take((size_t)Mpad * D * 2);
-    h16* sh_a = train ? nullptr : (h16*)take((size_t)Mpad * MLP * 2);
-    h16* sh_t = train ? nullptr : (h16*)take((size_t)Mpad * kext_max * 2);
+    h16* sh_h = train ? nullptr : cv.take<h16>((size_t)Mpad * D * 2);
+    h16* sh_a = train ? nullptr : cv.take<h16>((size_t)Mpad * MLP * 2);
+    h16* sh_t = train ? nullptr : cv.take<h16>((size_t)Mpad * kext_max * 2);
     for (int l = 0; l < L; ++l) {
-        w.h1[l] = train ? (h16*)take((size_t)Mpad * D * 2) : sh_h;
-        w.h2[l] = train ? (h16*)take((size_t)Mpad * D * 2) : sh_h;
-        w.a[l] = train ? (h16*)take((size_t)Mpad * MLP * 2) : sh_a;
-        w.qkv[l] = (h16*)take((size_t)Mpad * 3 * D * 2);
-        w.ctx[l] = (h16*)take((size_t)Mpad * D * 2);
-        w.z[l] = (h16*)take((size_t)Mpad * MLP * 2);
+        w.h1[l] = train ? cv.take<h16>((size_t)Mpad * D * 2) : sh_h;
+        w.h2[l] = train ? cv.take<h16>((size_t)Mpad * D * 2) : sh_h;
+        w.a[l] = train ? cv.take<h16>((size_t)Mpad * MLP * 2) : sh_a;
+        w.qkv[l] = cv.take<h16>((size_t)Mpad * 3 * D * 2);
+        w.ctx[l] = cv.take<h16>((size_t)Mpad * D * 2);
+        w.z[l] = cv.take<h16>((size_t)Mpad * MLP * 2);
         for (int k = 0; k < 4; ++k)
-            w.t[k][l] = train ? (h16*)take((size_t)Mpad * kext_max * 2) : sh_t;
+            w.t[k][l] = train ? cv.take<h16>((size_t)Mpad * kext_max * 2) : sh_t;
     }
     {   // compact CLS-row buffers of the last layer
         Workspace::Cls& c = w.c;
         const int64_t Bc = round_up(B, 128);
         c.Bc = Bc;
-        c.x0 = (float*)take((size_t)Bc * D * 4); c.x1 = (float*)take((size_t)Bc * D * 4); c.x2 = (float*)take((size_t)Bc * D * 4);
-        c.mean = (float*)take((size_t)Bc * 4); c.rstd = (float*)take((size_t)Bc * 4);
-        c.lse = (float*)take((size_t)B * m->H * 4);
-        c.ctx = (h16*)take((size_t)Bc * D * 2); c.delta = (h16*)take((size_t)Bc * D * 2); c.h2 = (h16*)take((size_t)Bc * D * 2);
-        c.a = (h16*)take((size_t)Bc * MLP * 2); c.z = (h16*)take((size_t)Bc * MLP * 2);
-        c.t = (h16*)take((size_t)Bc * kext_max * 2);
-        c.dres[0] = (float*)take((size_t)Bc * D * 4); c.dres[1] = (float*)take((size_t)Bc * D * 4);
-        c.dres_h = (h16*)take((size_t)Bc * D * 2); c.dh = (h16*)take((size_t)Bc * D * 2); c.dctx = (h16*)take((size_t)Bc * D * 2);
-        c.dz = (h16*)take((size_t)Bc * MLP * 2); c.u = (h16*)take((size_t)Bc * kext_max * 2);
+        c.x0 = cv.take<float>((size_t)Bc * D * 4); c.x1 = cv.take<float>((size_t)Bc * D * 4); c.x2 = cv.take<float>((size_t)Bc * D * 4);
+        c.mean = cv.take<float>((size_t)Bc * 4); c.rstd = cv.take<float>((size_t)Bc * 4);
+        c.lse = cv.take<float>((size_t)B * m->H * 4);
+        c.ctx = cv.take<h16>((size_t)Bc * D * 2); c.delta = cv.take<h16>((size_t)Bc * D * 2); c.h2 = cv.take<h16>((size_t)Bc * D * 2);
+        c.a = cv.take<h16>((size_t)Bc * MLP * 2); c.z = cv.take<h16>((size_t)Bc * MLP * 2);
+        c.t = cv.take<h16>((size_t)Bc * kext_max * 2);
+        c.dres[0] = cv.take<float>((size_t)Bc * D * 4); c.dres[1] = cv.take<float>((size_t)Bc * D * 4);
+        c.dres_h = cv.take<h16>((size_t)Bc * D * 2); c.dh = cv.take<h16>((size_t)Bc * D * 2); c.dctx = cv.take<h16>((size_t)Bc * D * 2);
+        c.dz = cv.take<h16>((size_t)Bc * MLP * 2); c.u = cv.take<h16>((size_t)Bc * kext_max * 2);
     }
-    w.dres_h = (h16*)take((size_t)Mpad * D * 2);
-    w.dh = (h16*)take((size_t)Mpad * D * 2);
-    w.dctx = (h16*)take((size_t)Mpad * D * 2);
-    w.dqkv = (h16*)take((size_t)Mpad * 3 * D * 2);
-    w.dz = (h16*)take((size_t)Mpad * MLP * 2);
-    w.u = (h16*)take((size_t)Mpad * kext_max * 2);
-    w.xd = train ? (h16*)take((size_t)Mpad * MLP * 2) : nullptr;
+    w.dres_h = cv.take<h16>((size_t)Mpad * D * 2);
+    w.dh = cv.take<h16>((size_t)Mpad * D * 2);
+    w.dctx = cv.take<h16>((size_t)Mpad * D * 2);
+    w.dqkv = cv.take<h16>((size_t)Mpad * 3 * D * 2);
+    w.dz = cv.take<h16>((size_t)Mpad * MLP * 2);
+    w.u = cv.take<h16>((size_t)Mpad * kext_max * 2);
+    w.xd = train ? cv.take<h16>((size_t)Mpad * MLP * 2) : nullptr;
     // per-chunk copies of the LoRA gradient (deterministic weight gradients: lora_grad.hip); the LoRA parameters are the
     // first cls_w_off elements of the flat buffer
-    w.wg_slab = train && m->cls_w_off > 0 ? (float*)take((size_t)lora_wgrad_chunks((int)((int64_t)B * m->T)) * (size_t)m->cls_w_off * 4) : nullptr;
-    return w.bytes = off;
+    w.wg_slab = train && m->cls_w_off > 0 ? cv.take<float>((size_t)lora_wgrad_chunks((int)((int64_t)B * m->T)) * (size_t)m->cls_w_off * 4) : nullptr;
+    return w.bytes = cv.off;
 }
 static size_t carve_bytes(const vl_model* m, int B, int train) {
     Workspace scratch;
     return carve(m, scratch, B, train, nullptr);
-}
-
-static void drop_graphs(vl_model* m) {
-    for (GraphEntry& g : m->graphs) { (void)hipGraphExecDestroy(g.exec); if (g.exec1) (void)hipGraphExecDestroy(g.exec1); }
-    m->graphs.clear();
-}
-
-// the cache holds the 8 most recent captured iterations (PGD and APGD alike)
-static void remember_graph(vl_model* m, const GraphEntry& e) {
-    if (m->graphs.size() >= 8) {
-        (void)hipGraphExecDestroy(m->graphs.front().exec);
-        if (m->graphs.front().exec1) (void)hipGraphExecDestroy(m->graphs.front().exec1);
-        m->graphs.erase(m->graphs.begin());
-    }
-    m->graphs.push_back(e);
-    m->n_captures++;
-}
-
-static int chain_resources(vl_model* m) {
-    if (!m->side_stream) HIPCHK(hipStreamCreateWithFlags(&m->side_stream, hipStreamNonBlocking));
-    if (!m->ev_fork) HIPCHK(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
-    if (!m->ev_join) HIPCHK(hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming));
-    return VL_OK;
 }
 
 // Two-chain PGD (model.h): each half pass's activations for up to chain_images() images, carved behind the main workspace.
@@ -733,8 +699,10 @@ int vl_set_workspace(vl_model* m, void* wsp, size_t bytes) {
 }
 
 // ---- forward ---------------------------------------------------------------------------------
+}  // extern "C": forward_impl is shared with vit_attacks.hip under the build's namespace (model.h)
+
 // one forward of B images in pass `p`; on success p holds it (B, rows, norm, train, cls_only) and no loss yet
-static int forward_impl(vl_model* m, Pass& p, const float* x, int B, int normalise, int train, hipStream_t s) {
+int forward_impl(vl_model* m, Pass& p, const float* x, int B, int normalise, int train, hipStream_t s) {
     Workspace& w = p.ws;
     if (B <= 0 || B > w.max_batch) return fail(VL_ERR_STATE, "batch %d exceeds planned workspace (%d)", B, w.max_batch);
     if (train && !w.train) return fail(VL_ERR_STATE, "workspace was not planned for training");
@@ -824,6 +792,8 @@ static int forward_impl(vl_model* m, Pass& p, const float* x, int B, int normali
     return VL_OK;
 }
 
+extern "C" {
+
 int vl_forward(vl_model* m, const float* x, int batch, int normalise, int train, float* logits_out, void* stream) {
     if (!m || !x) return fail(VL_ERR_ARG, "null argument");
     if (!m->main.ws.max_batch) return fail(VL_ERR_STATE, "no workspace: call vl_plan + vl_set_workspace first");
@@ -869,13 +839,12 @@ int vl_loss_ce(vl_model* m, const int64_t* labels, float* loss_out, void* stream
     return VL_OK;
 }
 
+}  // extern "C": backward_impl is shared with vit_attacks.hip, as forward_impl
+
 // ---- backward --------------------------------------------------------------------------------
 // shared dgrad chain; flat_grad != null additionally produces the LoRA / classifier gradients,
-// grad_x != null the input gradient.
-// K10 fused into the patch-gradient epilogue: the pixel gradient never goes to HBM (vl_pgd_attack; vl_pgd_step stays the ABI entry)
-struct PgdFuse { float* adv; const float* x0; float eps, alpha; };
-
-static int backward_impl(vl_model* m, Pass& p, float* grad_x, float* flat_grad, hipStream_t s, const PgdFuse* pf = nullptr) {
+// grad_x != null the input gradient, pf != null the PGD step inside the patch-gradient epilogue (PgdFuse: model.h).
+int backward_impl(vl_model* m, Pass& p, float* grad_x, float* flat_grad, hipStream_t s, const PgdFuse* pf) {
     Workspace& w = p.ws;
     if (!p.have_loss) return fail(VL_ERR_STATE, "backward before vl_loss_ce");
     const int B = p.B, D = m->D, L = m->L, T = m->T, MLP = m->MLP, r = m->r;
@@ -995,6 +964,8 @@ static int backward_impl(vl_model* m, Pass& p, float* grad_x, float* flat_grad, 
     return VL_OK;
 }
 
+extern "C" {
+
 // Synchronises `stream` and reports what the kernels enqueued so far flagged (bad label: VL_ERR_ARG; a gradient that left the
 // fp16 range or is NaN: VL_ERR_NONFINITE).  Other entry points report the same at their NEXT call without synchronising.
 int vl_check_errors(vl_model* m, void* stream) {
@@ -1088,493 +1059,7 @@ int vl_backward_lora(vl_model* m, float* flat_grad_out, void* stream) {
     return backward_api(m, nullptr, flat_grad_out, (hipStream_t)stream);
 }
 
-// ---- attacks ---------------------------------------------------------------------------------
-#ifndef VL_BF16
-int vl_pgd_step(float* adv, const float* x0, const float* grad, float eps, float alpha, float lo, float hi, int64_t n,
-                void* stream) {
-    if (!adv || !x0 || !grad || n <= 0) return fail(VL_ERR_ARG, "bad argument");
-    k_pgd_step(adv, x0, grad, eps, alpha, lo, hi, n, (hipStream_t)stream);
-    return VL_OK;
-}
-#endif
-
-#ifndef VL_BF16
-int vl_pgd_init(float* adv, const float* x0, float eps, float lo, float hi, uint64_t seed, int64_t n, void* stream) {
-    if (!adv || !x0 || n <= 0) return fail(VL_ERR_ARG, "bad argument");
-    k_pgd_init(adv, x0, eps, lo, hi, seed, n, (hipStream_t)stream);
-    return VL_OK;
-}
-#endif
-
-// VITLORA_GRAPH_DUMP=<file>: append the node list of a captured iteration (type, kernel name, grid, block, dynamic LDS)
-static void dump_graph(hipGraph_t graph) {
-    const char* path = env_graph_dump();
-    if (!path) return;
-    FILE* f = fopen(path, "a");
-    if (!f) return;
-    size_t n = 0;
-    if (hipGraphGetNodes(graph, nullptr, &n) != hipSuccess) { fclose(f); return; }
-    std::vector<hipGraphNode_t> nodes(n);
-    if (n && hipGraphGetNodes(graph, nodes.data(), &n) != hipSuccess) { fclose(f); return; }
-    fprintf(f, "graph %zu nodes\n", n);
-    for (size_t i = 0; i < n; ++i) {
-        hipGraphNodeType ty;
-        if (hipGraphNodeGetType(nodes[i], &ty) != hipSuccess) { fprintf(f, "%zu ?\n", i); continue; }
-        if (ty == hipGraphNodeTypeKernel) {
-            hipKernelNodeParams kp;
-            memset(&kp, 0, sizeof kp);
-            if (hipGraphKernelNodeGetParams(nodes[i], &kp) != hipSuccess) { fprintf(f, "%zu kernel ?\n", i); continue; }
-            const char* nm = hipKernelNameRefByPtr(kp.func, nullptr);
-            fprintf(f, "%zu kernel %s grid %u,%u,%u block %u lds %u\n", i, nm ? nm : "?", kp.gridDim.x, kp.gridDim.y, kp.gridDim.z,
-                    kp.blockDim.x, kp.sharedMemBytes);
-        } else if (ty == hipGraphNodeTypeMemset) {
-            hipMemsetParams mp;
-            memset(&mp, 0, sizeof mp);
-            if (hipGraphMemsetNodeGetParams(nodes[i], &mp) != hipSuccess) { fprintf(f, "%zu memset ?\n", i); continue; }
-            fprintf(f, "%zu memset dst %p value %u elem %u width %zu height %zu\n", i, mp.dst, mp.value, mp.elementSize, mp.width, mp.height);
-        } else {
-            fprintf(f, "%zu type %d\n", i, (int)ty);
-        }
-    }
-    {   // dependency edges as index pairs
-        size_t ne = 0;
-        if (hipGraphGetEdges(graph, nullptr, nullptr, &ne) == hipSuccess && ne) {
-            std::vector<hipGraphNode_t> from(ne), to(ne);
-            if (hipGraphGetEdges(graph, from.data(), to.data(), &ne) == hipSuccess) {
-                auto idx = [&](hipGraphNode_t x) -> long { for (size_t i = 0; i < n; ++i) if (nodes[i] == x) return (long)i; return -1; };
-                fprintf(f, "edges %zu:", ne);
-                for (size_t e = 0; e < ne; ++e) fprintf(f, " %ld>%ld", idx(from[e]), idx(to[e]));
-                fprintf(f, "\n");
-            }
-        } else fprintf(f, "edges 0\n");
-    }
-    (void)hipGetLastError();
-    fclose(f);
-}
-
-static int pgd_iteration(vl_model* m, Pass& p, const float* x0, const int64_t* labels, int B, float eps, float alpha, float* adv,
-                         hipStream_t s) {
-    int rc = forward_impl(m, p, adv, B, 1, 0, s);
-    if (rc) return rc;
-    k_ce_loss(p.ws.logits, labels, B, m->C, p.ws.dlogits, p.ws.loss_img, p.ws.loss, m->err_flag, s);
-    p.have_loss = 1;
-    if (m->fuse_pgd && !m->f32) {
-        const PgdFuse pf = {adv, x0, eps, alpha};
-        return backward_impl(m, p, nullptr, nullptr, s, &pf);
-    }
-    rc = backward_impl(m, p, p.ws.grad_img, nullptr, s);
-    if (rc) return rc;
-    k_pgd_step(adv, x0, p.ws.grad_img, eps, alpha, 0.f, 1.f, (int64_t)B * 3 * m->S * m->S, s, m->err_flag);
-    return VL_OK;
-}
-
-int vl_pgd_attack(vl_model* m, const float* x0, const int64_t* labels, int batch, float eps, float alpha, int steps,
-                  int random_start, uint64_t seed, float* adv_out, void* stream) {
-    if (!m || !x0 || !labels || !adv_out) return fail(VL_ERR_ARG, "bad argument");
-    if (!m->main.ws.max_batch) return fail(VL_ERR_STATE, "no workspace");
-    if (batch <= 0 || batch > m->main.ws.max_batch) return fail(VL_ERR_STATE, "batch exceeds planned workspace");
-    hipStream_t s = (hipStream_t)stream;
-    int rc = check_async(m);
-    if (rc) return rc;
-    if (m->dirty && (rc = vl_lora_commit(m, stream))) return rc;     // the attack sees the CURRENT adapters
-    Workspace& w = m->main.ws;
-    const int64_t n = (int64_t)batch * 3 * m->S * m->S;
-    // Persistent staging: the captured iteration only ever reads / writes the workspace's x0 / labels / adv buffers,
-    // so ONE executable graph per (batch, eps, alpha) serves every batch of a run whatever tensors the caller passes
-    // (3 device copies of the image batch per attack: < 0.1 % of a PGD-20 attack).
-    HIPCHK(hipMemcpyAsync(w.stage_x0, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(w.stage_labels, labels, (size_t)batch * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    if (random_start) k_pgd_init(w.stage_adv, w.stage_x0, eps, 0.f, 1.f, seed, n, s);
-    else HIPCHK(hipMemcpyAsync(w.stage_adv, w.stage_x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    // two half-batch chains as parallel branches of the captured iteration (model.h): by batch size, or as "pgd_chains" says
-    float* const sx0 = w.stage_x0; float* const sadv = w.stage_adv; int64_t* const slab = w.stage_labels;    // the MAIN staging buffers
-    const int b0 = (batch + 1) / 2, b1 = batch - b0;
-    const bool chain_fits = m->chain_batch > 0 && batch >= 2 && b0 <= m->chain_batch;
-    const int chains = (chain_fits && (m->pgd_chains == 2 || (m->pgd_chains == 0 && batch <= vl_model::CHAIN_MAX_BATCH))) ? 2 : 1;
-    // one PGD iteration of half pass c over its slice of the staged batch
-    const int64_t off1 = (int64_t)b0 * 3 * m->S * m->S;
-    auto half_iteration = [&](int c, Pass& h, hipStream_t sc) -> int {
-        return pgd_iteration(m, h, sx0 + (c ? off1 : 0), slab + (c ? b0 : 0), c ? b1 : b0, eps, alpha, sadv + (c ? off1 : 0), sc);
-    };
-    // one PGD iteration of the whole batch, enqueued on s (chains == 2: second half on the side stream between a fork and a join event)
-    auto iteration = [&]() -> int {
-        if (chains == 1) return pgd_iteration(m, m->main, sx0, slab, batch, eps, alpha, sadv, s);
-        return on_both_halves(m, s, half_iteration);
-    };
-    m->fwd_chains = 0;
-    if (chains == 2 && (rc = chain_resources(m))) return rc;
-    if (steps > 0) {
-        if (!m->use_graph || g_prof || g_poison_lds) {
-            for (int i = 0; i < steps; ++i)
-                if ((rc = iteration())) return rc;
-            if ((rc = check_launch("vl_pgd_attack"))) return rc;
-        } else {
-            hipGraphExec_t exec = nullptr, exec1 = nullptr;
-            for (GraphEntry& g : m->graphs)
-                if (g.kind == 0 && g.B == batch && g.eps == eps && g.alpha == alpha && g.chains == chains) { exec = g.exec; exec1 = g.exec1; break; }
-            if (!exec) {
-                // Captured cold: nothing has to run eagerly first.  (Round 2 ran the first iteration eagerly because replays of
-                // a graph captured in a fresh process differed from the eager result.  Cause, established in round 3 with
-                // tools/cold_capture_diag.py: the two hipMemsetAsync nodes of the backward did not take effect on replays when
-                // they were captured before the runtime's fill kernel had ever run; the first launch passed only because the
-                // workspace was still zero.  They are k_zero kernel nodes now: profiles/r03_cold_capture_*.txt.)
-                // capture on a private stream (the caller's may be the legacy default stream, which cannot
-                // capture); nothing executes during capture, the graph is launched on the caller's stream.
-                if (!m->cap_stream) HIPCHK(hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking));
-                // one captured iteration per chain: chains == 2 gives two graphs, each over its half of the staged batch and its
-                // own activation workspace, replayed on two streams that meet only at the start and the end of the attack
-                auto capture = [&](int c, hipGraphExec_t* out) -> int {
-                    hipGraph_t graph = nullptr;
-                    (void)hipGetLastError();
-                    HIPCHK(hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeThreadLocal));
-                    const int rcc = chains == 1 ? pgd_iteration(m, m->main, sx0, slab, batch, eps, alpha, sadv, m->cap_stream)
-                                                : half_iteration(c, m->half[c], m->cap_stream);
-                    hipError_t e = hipStreamEndCapture(m->cap_stream, &graph);
-                    if (rcc) { if (graph) (void)hipGraphDestroy(graph); return rcc; }
-                    if (e != hipSuccess) return fail(VL_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-                    dump_graph(graph);
-                    e = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
-                    (void)hipGraphDestroy(graph);
-                    if (e != hipSuccess) return fail(VL_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-                    return VL_OK;
-                };
-                if ((rc = capture(0, &exec))) return rc;
-                if (chains == 2 && (rc = capture(1, &exec1))) { (void)hipGraphExecDestroy(exec); return rc; }
-                remember_graph(m, {batch, eps, alpha, exec, chains, exec1});
-            }
-            if (chains == 2) {
-                HIPCHK(hipEventRecord(m->ev_fork, s));
-                HIPCHK(hipStreamWaitEvent(m->side_stream, m->ev_fork, 0));
-            }
-            for (int i = 0; i < steps; ++i) {
-                HIPCHK(hipGraphLaunch(exec, s));
-                if (chains == 2) HIPCHK(hipGraphLaunch(exec1, m->side_stream));
-            }
-            if (chains == 2) {
-                HIPCHK(hipEventRecord(m->ev_join, m->side_stream));
-                HIPCHK(hipStreamWaitEvent(s, m->ev_join, 0));
-            }
-        }
-        // two chains leave no forward of the whole batch in the main pass: a backward call needs its own forward and loss
-        if (chains == 2) m->main.B = m->main.have_loss = 0;
-    }
-    HIPCHK(hipMemcpyAsync(adv_out, w.stage_adv, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return VL_OK;
-}
-
-// ---- Auto-PGD (APGD-CE, L-inf; include/vitlora.h) --------------------------
-// Everything the attack keeps between iterations, carved from the caller's scratch (base == nullptr: size only).
-struct ApgdLayout {
-    float *x0, *x_adv, *x_old, *x_best, *x_best_adv, *grad_best;
-    int64_t* labels;
-    ApgdState st;
-};
-static size_t apgd_carve(const vl_model* m, int B, int N, char* base, ApgdLayout& L) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) -> char* {
-        char* p = base ? base + off : nullptr;
-        off += (size_t)round_up((int64_t)bytes, 256);
-        return p;
-    };
-    const size_t img = (size_t)B * 3 * m->S * m->S * 4, row = (size_t)B * 4;
-    L.x0 = (float*)take(img); L.x_adv = (float*)take(img); L.x_old = (float*)take(img);
-    L.x_best = (float*)take(img); L.x_best_adv = (float*)take(img); L.grad_best = (float*)take(img);
-    L.labels = (int64_t*)take((size_t)B * 8);
-    L.st.ctr = (int32_t*)take(16);
-    L.st.sched = (ApgdSched*)take((size_t)(N + 1) * sizeof(ApgdSched));
-    L.st.step = (float*)take(row); L.st.loss_best = (float*)take(row); L.st.loss_best_last = (float*)take(row);
-    L.st.reduced_last = (int32_t*)take(row); L.st.robust = (int32_t*)take(row); L.st.flags = (uint32_t*)take(row);
-    L.st.tr_loss = (float*)take((size_t)(N + 1) * row); L.st.tr_step = (float*)take((size_t)N * row);
-    L.st.tr_pred = (int32_t*)take((size_t)(N + 1) * row);
-    return off;
-}
-static int apgd_check_scratch(const vl_model* m, const void* scratch, size_t bytes, int batch, int steps) {
-    if (!m->main.ws.max_batch) return fail(VL_ERR_STATE, "no workspace");
-    if (batch <= 0 || batch > m->main.ws.max_batch) return fail(VL_ERR_STATE, "batch exceeds planned workspace");
-    if (batch > 65535) return fail(VL_ERR_UNSUPPORTED, "APGD runs at most 65535 images per call (one grid row per image)");
-    if (steps < 1 || steps > 65535) return fail(VL_ERR_ARG, "steps must be 1 .. 65535");
-    if (!scratch || ((uintptr_t)scratch & 255)) return fail(VL_ERR_ARG, "scratch must be a 256-byte aligned device buffer");
-    ApgdLayout sz;
-    const size_t need = apgd_carve(m, batch, steps, nullptr, sz);
-    if (bytes < need) return fail(VL_ERR_ARG, "APGD scratch too small: %zu < %zu (vl_apgd_scratch_bytes)", bytes, need);
-    return VL_OK;
-}
-
-int vl_apgd_scratch_bytes(vl_model* m, int batch, int steps, size_t* bytes) {
-    if (!m || !bytes || batch <= 0 || steps < 1 || steps > 65535) return fail(VL_ERR_ARG, "bad argument");
-    ApgdLayout sz;
-    *bytes = apgd_carve(m, batch, steps, nullptr, sz);
-    return VL_OK;
-}
-
-// one APGD iteration in the main pass: evaluate x_adv (forward, CE, gradient to grad_img), then bookkeeping and the next point
-static int apgd_iteration(vl_model* m, const ApgdLayout& L, int B, int N, float eps, float rho, hipStream_t s) {
-    Pass& p = m->main;
-    int rc = forward_impl(m, p, L.x_adv, B, 1, 0, s);
-    if (rc) return rc;
-    k_ce_loss(p.ws.logits, L.labels, B, m->C, p.ws.dlogits, p.ws.loss_img, p.ws.loss, m->err_flag, s);
-    p.have_loss = 1;
-    if ((rc = backward_impl(m, p, p.ws.grad_img, nullptr, s))) return rc;
-    k_apgd_track(L.st, p.ws.loss_img, p.ws.logits, L.labels, B, m->C, N, eps, rho, s);
-    k_apgd_step(L.x_adv, L.x_old, L.x_best, L.x_best_adv, L.grad_best, L.x0, p.ws.grad_img, L.st.flags, L.st.step, B,
-                (int64_t)3 * m->S * m->S, eps, L.st.sched, L.st.ctr, N, 0.f, 0, s, m->err_flag);
-    return VL_OK;
-}
-
-int vl_apgd_attack(vl_model* m, const vl_apgd_args* a) {
-    if (!m || !a || !a->x0 || !a->labels) return fail(VL_ERR_ARG, "bad argument");
-    if (!(a->eps >= 0.f) || !(a->eps < INFINITY) || !(a->rho >= 0.f) || !(a->rho <= 1.f)) return fail(VL_ERR_ARG, "eps must be finite and >= 0, rho in [0, 1]");
-    int rc = apgd_check_scratch(m, a->scratch, a->scratch_bytes, a->batch, a->steps);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)a->stream;
-    if ((rc = check_async(m))) return rc;
-    if (m->dirty && (rc = vl_lora_commit(m, a->stream))) return rc;     // the attack sees the CURRENT adapters
-    const int B = a->batch, N = a->steps;
-    const float eps = a->eps, rho = a->rho;
-    ApgdLayout L;
-    apgd_carve(m, B, N, (char*)a->scratch, L);
-    const int64_t n_img = (int64_t)3 * m->S * m->S, n = (int64_t)B * n_img;
-    // staging, as vl_pgd_attack: the captured iteration only ever sees addresses inside the scratch and the workspace
-    HIPCHK(hipMemcpyAsync(L.x0, a->x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(L.labels, a->labels, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    if (a->x_init) k_apgd_start(L.x_adv, a->x_init, n, s);
-    else if (a->random_start) k_apgd_rand_init(L.x_adv, L.x0, eps, a->seed, B, n_img, s);
-    else k_apgd_start(L.x_adv, L.x0, n, s);
-    HIPCHK(hipMemcpyAsync(L.x_old, L.x_adv, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    k_apgd_sched(L.st.sched, L.st.ctr, N, s);
-    m->fwd_chains = 0;
-    if (!m->use_graph || g_prof || g_poison_lds) {
-        for (int j = 0; j <= N; ++j)
-            if ((rc = apgd_iteration(m, L, B, N, eps, rho, s))) return rc;
-        if ((rc = check_launch("vl_apgd_attack"))) return rc;
-    } else {
-        hipGraphExec_t exec = nullptr;
-        for (GraphEntry& g : m->graphs)
-            if (g.kind == 1 && g.B == B && g.eps == eps && g.steps == N && g.scratch == a->scratch && g.rho == rho) { exec = g.exec; break; }
-        if (!exec) {      // captured cold on the private stream, as the PGD iteration
-            if (!m->cap_stream) HIPCHK(hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking));
-            hipGraph_t graph = nullptr;
-            (void)hipGetLastError();
-            HIPCHK(hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeThreadLocal));
-            const int rcc = apgd_iteration(m, L, B, N, eps, rho, m->cap_stream);
-            hipError_t e = hipStreamEndCapture(m->cap_stream, &graph);
-            if (rcc) { if (graph) (void)hipGraphDestroy(graph); return rcc; }
-            if (e != hipSuccess) return fail(VL_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-            dump_graph(graph);
-            e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            if (e != hipSuccess) return fail(VL_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-            GraphEntry ge = {B, eps, 0.f, exec, 1, nullptr};
-            ge.kind = 1; ge.steps = N; ge.scratch = a->scratch; ge.rho = rho;
-            remember_graph(m, ge);
-        }
-        for (int j = 0; j <= N; ++j) HIPCHK(hipGraphLaunch(exec, s));
-    }
-    const size_t row = (size_t)B * 4;
-    if (a->x_best) HIPCHK(hipMemcpyAsync(a->x_best, L.x_best, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (a->x_best_adv) HIPCHK(hipMemcpyAsync(a->x_best_adv, L.x_best_adv, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (a->loss_best) HIPCHK(hipMemcpyAsync(a->loss_best, L.st.loss_best, row, hipMemcpyDeviceToDevice, s));
-    if (a->robust) HIPCHK(hipMemcpyAsync(a->robust, L.st.robust, row, hipMemcpyDeviceToDevice, s));
-    if (a->trace_loss) HIPCHK(hipMemcpyAsync(a->trace_loss, L.st.tr_loss, (size_t)(N + 1) * row, hipMemcpyDeviceToDevice, s));
-    if (a->trace_step) HIPCHK(hipMemcpyAsync(a->trace_step, L.st.tr_step, (size_t)N * row, hipMemcpyDeviceToDevice, s));
-    if (a->trace_pred) HIPCHK(hipMemcpyAsync(a->trace_pred, L.st.tr_pred, (size_t)(N + 1) * row, hipMemcpyDeviceToDevice, s));
-    return VL_OK;
-}
-
-int vl_debug_apgd_track(vl_model* m, const vl_apgd_track_case* c, void* stream) {
-    if (!m || !c || !c->loss_img || !c->logits || !c->labels) return fail(VL_ERR_ARG, "bad argument");
-    int rc = apgd_check_scratch(m, c->scratch, c->scratch_bytes, c->batch, c->steps);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    ApgdLayout L;
-    apgd_carve(m, c->batch, c->steps, (char*)c->scratch, L);
-    if (c->reset) k_apgd_sched(L.st.sched, L.st.ctr, c->steps, s);
-    k_apgd_track(L.st, c->loss_img, c->logits, c->labels, c->batch, m->C, c->steps, c->eps, c->rho, s);
-    HIPCHK(hipMemcpyAsync(L.st.ctr, L.st.ctr + 1, 4, hipMemcpyDeviceToDevice, s));      // what the step kernel does in the attack
-    const size_t row = (size_t)c->batch * 4;
-    if (c->step_out) HIPCHK(hipMemcpyAsync(c->step_out, L.st.step, row, hipMemcpyDeviceToDevice, s));
-    if (c->flags_out) HIPCHK(hipMemcpyAsync(c->flags_out, L.st.flags, row, hipMemcpyDeviceToDevice, s));
-    if (c->loss_best_out) HIPCHK(hipMemcpyAsync(c->loss_best_out, L.st.loss_best, row, hipMemcpyDeviceToDevice, s));
-    if (c->robust_out) HIPCHK(hipMemcpyAsync(c->robust_out, L.st.robust, row, hipMemcpyDeviceToDevice, s));
-    return VL_OK;
-}
-
-#ifndef VL_BF16
-int vl_apgd_step(float* x_adv, float* x_old, float* x_best, float* x_best_adv, float* grad_best, const float* x0,
-                 const float* grad, const uint32_t* flags, const float* step, int batch, int64_t image_elems, float eps,
-                 float a, int last, void* stream) {
-    if (!x_adv || !x_old || !x_best || !x_best_adv || !grad_best || !x0 || !grad || !flags || !step || batch <= 0 || batch > 65535 ||
-        image_elems <= 0 || image_elems % 4)
-        return fail(VL_ERR_ARG, "bad argument (image_elems must be a positive multiple of 4, batch 1 .. 65535)");
-    const void* ptrs[] = {x_adv, x_old, x_best, x_best_adv, grad_best, x0, grad};
-    for (const void* p : ptrs)
-        if ((uintptr_t)p & 15) return fail(VL_ERR_ARG, "image pointers must be 16-byte aligned");
-    k_apgd_step(x_adv, x_old, x_best, x_best_adv, grad_best, x0, grad, flags, step, batch, image_elems, eps, nullptr, nullptr, 0, a,
-                last ? 1 : 0, (hipStream_t)stream);
-    return VL_OK;
-}
-#endif
-
-// ---- Square attack (L-inf, margin loss; include/vitlora.h) ----------------
-// Everything the attack keeps between replays, carved from the caller's scratch (base == nullptr: size only).
-struct SquareLayout {
-    float *x0, *x_cur, *x_best;
-    int64_t* labels;
-    SquareState st;
-};
-static size_t square_carve(const vl_model* m, int B, int N, char* base, SquareLayout& L) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) -> char* {
-        char* p = base ? base + off : nullptr;
-        off += (size_t)round_up((int64_t)bytes, 256);
-        return p;
-    };
-    const size_t img = (size_t)B * 3 * m->S * m->S * 4, row = (size_t)B * 4;
-    L.x0 = (float*)take(img); L.x_cur = (float*)take(img); L.x_best = (float*)take(img);
-    L.labels = (int64_t*)take((size_t)B * 8);
-    L.st.ctr = (int32_t*)take(16);
-    L.st.par = (SquareParams*)take(sizeof(SquareParams));
-    L.st.side = (int32_t*)take((size_t)(N + 1) * 4);
-    L.st.margin_min = (float*)take(row); L.st.queries = (int32_t*)take(row); L.st.robust = (int32_t*)take(row);
-    L.st.flags = (uint32_t*)take(row);
-    L.st.win_prev = (int32_t*)take(4 * row); L.st.win_next = (int32_t*)take(4 * row);
-    L.st.tr_margin = (float*)take((size_t)(N + 1) * row);
-    L.st.tr_win = (int32_t*)take((size_t)N * 4 * row);
-    return off;
-}
-static int square_check_scratch(const vl_model* m, const void* scratch, size_t bytes, int batch, int n_queries) {
-    if (m->C < 2) return fail(VL_ERR_UNSUPPORTED, "the margin loss needs num_labels >= 2");
-    if (!m->main.ws.max_batch) return fail(VL_ERR_STATE, "no workspace");
-    if (batch <= 0 || batch > m->main.ws.max_batch) return fail(VL_ERR_STATE, "batch exceeds planned workspace");
-    if (batch > 65535) return fail(VL_ERR_UNSUPPORTED, "Square runs at most 65535 images per call (one grid row per image)");
-    if (n_queries < 1 || n_queries > 65535) return fail(VL_ERR_ARG, "n_queries must be 1 .. 65535");
-    if (!scratch || ((uintptr_t)scratch & 255)) return fail(VL_ERR_ARG, "scratch must be a 256-byte aligned device buffer");
-    SquareLayout sz;
-    const size_t need = square_carve(m, batch, n_queries, nullptr, sz);
-    if (bytes < need) return fail(VL_ERR_ARG, "Square scratch too small: %zu < %zu (vl_square_scratch_bytes)", bytes, need);
-    return VL_OK;
-}
-
-int vl_square_scratch_bytes(vl_model* m, int batch, int n_queries, size_t* bytes) {
-    if (!m || !bytes || batch <= 0 || n_queries < 1 || n_queries > 65535) return fail(VL_ERR_ARG, "bad argument");
-    SquareLayout sz;
-    *bytes = square_carve(m, batch, n_queries, nullptr, sz);
-    return VL_OK;
-}
-
-// one replay in the main pass: evaluate x_cur (eval-mode forward, the last layer on the CLS rows alone), then the bookkeeping and
-// the pixels of the two windows
-static int square_iteration(vl_model* m, const SquareLayout& L, int B, int N, float eps, hipStream_t s) {
-    Pass& p = m->main;
-    const int rc = forward_impl(m, p, L.x_cur, B, 1, 0, s);
-    if (rc) return rc;
-    if (m->square_bare) return VL_OK;
-    k_square_track(L.st, p.ws.logits, L.labels, B, m->C, m->S, N, s, m->err_flag);
-    k_square_step(L.x_cur, L.x_best, L.x0, L.st.flags, L.st.win_prev, L.st.win_next, B, m->S, eps, L.st.ctr, N, s);
-    return VL_OK;
-}
-
-int vl_square_attack(vl_model* m, const vl_square_args* a) {
-    if (!m || !a) return fail(VL_ERR_ARG, "bad argument");
-    if (a->first < 0 || a->count < 1) return fail(VL_ERR_ARG, "first must be >= 0 and count >= 1");
-    if (a->first == 0 && (!a->x0 || !a->labels)) return fail(VL_ERR_ARG, "x0 and labels are needed when first == 0");
-    if (!(a->eps >= 0.f) || !(a->eps < INFINITY) || !(a->p_init > 0.f) || !(a->p_init <= 1.f))
-        return fail(VL_ERR_ARG, "eps must be finite and >= 0, p_init in (0, 1]");
-    int rc = square_check_scratch(m, a->scratch, a->scratch_bytes, a->batch, a->n_queries);
-    if (rc) return rc;
-    if ((int64_t)a->first + a->count > (int64_t)a->n_queries + 1) return fail(VL_ERR_ARG, "first + count exceeds the n_queries + 1 replays of the schedule");
-    hipStream_t s = (hipStream_t)a->stream;
-    if ((rc = check_async(m))) return rc;
-    if (m->dirty && (rc = vl_lora_commit(m, a->stream))) return rc;     // the attack sees the CURRENT adapters
-    const int B = a->batch, N = a->n_queries;
-    const float eps = a->eps;
-    SquareLayout L;
-    square_carve(m, B, N, (char*)a->scratch, L);
-    const int64_t n = (int64_t)B * 3 * m->S * m->S;
-    if (a->first == 0) {
-        // staging, as vl_pgd_attack: the captured iteration only ever sees addresses inside the scratch and the workspace
-        HIPCHK(hipMemcpyAsync(L.x0, a->x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpyAsync(L.labels, a->labels, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-        SquareSched sc;
-        square_schedule(m->S, N, a->p_init, &sc);
-        k_square_sched(L.st, sc, N, a->seed, a->image_offset, s);
-        k_square_init(L.x_cur, L.x_best, L.x0, L.st.par, B, m->S, eps, s);
-    }
-    m->fwd_chains = 0;
-    if (!m->use_graph || g_prof || g_poison_lds) {
-        for (int j = 0; j < a->count; ++j)
-            if ((rc = square_iteration(m, L, B, N, eps, s))) return rc;
-        if ((rc = check_launch("vl_square_attack"))) return rc;
-    } else {
-        hipGraphExec_t exec = nullptr;
-        for (GraphEntry& g : m->graphs)
-            if (g.kind == 2 && g.B == B && g.eps == eps && g.steps == N && g.scratch == a->scratch) { exec = g.exec; break; }
-        if (!exec) {      // captured cold on the private stream, as the PGD iteration
-            if (!m->cap_stream) HIPCHK(hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking));
-            hipGraph_t graph = nullptr;
-            (void)hipGetLastError();
-            HIPCHK(hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeThreadLocal));
-            const int rcc = square_iteration(m, L, B, N, eps, m->cap_stream);
-            hipError_t e = hipStreamEndCapture(m->cap_stream, &graph);
-            if (rcc) { if (graph) (void)hipGraphDestroy(graph); return rcc; }
-            if (e != hipSuccess) return fail(VL_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-            dump_graph(graph);
-            e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            if (e != hipSuccess) return fail(VL_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-            GraphEntry ge = {B, eps, 0.f, exec, 1, nullptr};
-            ge.kind = 2; ge.steps = N; ge.scratch = a->scratch;
-            remember_graph(m, ge);
-        }
-        for (int j = 0; j < a->count; ++j) HIPCHK(hipGraphLaunch(exec, s));
-    }
-    const size_t row = (size_t)B * 4;
-    const int done = a->first + a->count;          // replays 0 .. done - 1 have run
-    if (a->x_best) HIPCHK(hipMemcpyAsync(a->x_best, L.x_best, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (a->margin_min) HIPCHK(hipMemcpyAsync(a->margin_min, L.st.margin_min, row, hipMemcpyDeviceToDevice, s));
-    if (a->queries) HIPCHK(hipMemcpyAsync(a->queries, L.st.queries, row, hipMemcpyDeviceToDevice, s));
-    if (a->robust) HIPCHK(hipMemcpyAsync(a->robust, L.st.robust, row, hipMemcpyDeviceToDevice, s));
-    if (a->trace_margin) HIPCHK(hipMemcpyAsync(a->trace_margin, L.st.tr_margin, (size_t)done * row, hipMemcpyDeviceToDevice, s));
-    if (a->trace_win) HIPCHK(hipMemcpyAsync(a->trace_win, L.st.tr_win, (size_t)std::min(done, N) * 4 * row, hipMemcpyDeviceToDevice, s));
-    return VL_OK;
-}
-
-int vl_debug_square_track(vl_model* m, const vl_square_track_case* c, void* stream) {
-    if (!m || !c || !c->logits || !c->labels) return fail(VL_ERR_ARG, "bad argument");
-    if (c->reset && (!(c->p_init > 0.f) || !(c->p_init <= 1.f))) return fail(VL_ERR_ARG, "p_init in (0, 1]");
-    int rc = square_check_scratch(m, c->scratch, c->scratch_bytes, c->batch, c->n_queries);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    SquareLayout L;
-    square_carve(m, c->batch, c->n_queries, (char*)c->scratch, L);
-    if (c->reset) {
-        SquareSched sc;
-        square_schedule(m->S, c->n_queries, c->p_init, &sc);
-        k_square_sched(L.st, sc, c->n_queries, c->seed, c->image_offset, s);
-    }
-    k_square_track(L.st, c->logits, c->labels, c->batch, m->C, m->S, c->n_queries, s, nullptr);
-    HIPCHK(hipMemcpyAsync(L.st.ctr, L.st.ctr + 1, 4, hipMemcpyDeviceToDevice, s));      // what the step kernel does in the attack
-    const size_t row = (size_t)c->batch * 4;
-    if (c->flags_out) HIPCHK(hipMemcpyAsync(c->flags_out, L.st.flags, row, hipMemcpyDeviceToDevice, s));
-    if (c->win_prev_out) HIPCHK(hipMemcpyAsync(c->win_prev_out, L.st.win_prev, 4 * row, hipMemcpyDeviceToDevice, s));
-    if (c->win_next_out) HIPCHK(hipMemcpyAsync(c->win_next_out, L.st.win_next, 4 * row, hipMemcpyDeviceToDevice, s));
-    if (c->margin_min_out) HIPCHK(hipMemcpyAsync(c->margin_min_out, L.st.margin_min, row, hipMemcpyDeviceToDevice, s));
-    if (c->queries_out) HIPCHK(hipMemcpyAsync(c->queries_out, L.st.queries, row, hipMemcpyDeviceToDevice, s));
-    return VL_OK;
-}
-
-#ifndef VL_BF16
-int vl_square_step(float* x_cur, float* x_best, const float* x0, const uint32_t* flags, const int32_t* win_prev,
-                   const int32_t* win_next, int batch, int image_size, float eps, void* stream) {
-    if (!x_cur || !x_best || !x0 || !flags || !win_prev || !win_next || batch <= 0 || batch > 65535 || image_size <= 0 ||
-        image_size > 8192)
-        return fail(VL_ERR_ARG, "bad argument (batch 1 .. 65535, image_size 1 .. 8192)");
-    if (!(eps >= 0.f) || !(eps < INFINITY)) return fail(VL_ERR_ARG, "eps must be finite and >= 0");
-    k_square_step(x_cur, x_best, x0, flags, win_prev, win_next, batch, image_size, eps, nullptr, 0, (hipStream_t)stream);
-    return VL_OK;
-}
-#endif
-
+// ---- handle-less utilities (the attacks: vit_attacks.hip) ------------------------------------
 #ifndef VL_BF16
 int vl_adam_step(float* param, const float* grad, float* m1, float* m2, float lr, float b1, float b2, float eps, int t,
                  int64_t n, void* stream) {
@@ -1946,7 +1431,7 @@ int vl_debug_set_cus(vl_model* m, int cus) {
     return VL_OK;
 }
 
-// Diagnostic switches of a handle (tests, A/B timing); every change drops the cached PGD graphs.
+// Diagnostic switches of a handle (tests, A/B timing); every change drops the cached attack graphs.
 //   "dead_rows" 1 (default): eval-mode forwards run the last layer on the CLS rows only; 0: every row of every layer
 //   "fuse_pgd"  1 (default): vl_pgd_attack applies the PGD step inside the patch-gradient GEMM epilogue; 0: gradient to HBM + K10
 //   "resid_epi" 1 (default): the residual add of the 16-bit stream sits in the o / fc2 GEMM epilogue; 0: in the LayerNorm after it

@@ -127,15 +127,10 @@ int f32_debug_attention(const vl_attn_case* c, hipStream_t s) {
                           s, mfma);
 }
 
-size_t f32_carve(const vl_model* m, Workspace& w, int train, char* base, size_t off0) {
+size_t f32_carve(const vl_model* m, Workspace& w, int train, Carver& cv) {
     const int D = m->D, L = m->L, MLP = m->MLP;
     const int64_t Mpad = w.Mpad, Mppad = w.Mppad;
-    size_t off = off0;
-    auto take = [&](size_t bytes) -> float* {
-        char* p = base ? base + off : nullptr;
-        off += (size_t)round_up((int64_t)bytes, 256);
-        return (float*)p;
-    };
+    auto take = [&](size_t bytes) { return cv.take<float>(bytes); };
     int kext_max = 64;
     for (int k = 0; k < 4; ++k) if (m->layers[0].lin[k].kext > kext_max) kext_max = m->layers[0].lin[k].kext;
     w.f_patches = take((size_t)Mppad * m->PK * 4);
@@ -163,7 +158,7 @@ size_t f32_carve(const vl_model* m, Workspace& w, int train, char* base, size_t 
     // alone until round 4, the patch gradient then ran past the end of the workspace)
     w.f_tmp = take(std::max((size_t)Mpad * MLP, (size_t)Mppad * m->PK) * 4);
     w.f_xd = train ? take((size_t)Mpad * MLP * 4) : nullptr;
-    return off;
+    return cv.off;
 }
 
 int f32_forward(vl_model* m, Pass& p, const float* x, int B, int normalise, hipStream_t s) {

@@ -298,15 +298,16 @@ class Engine:
         check(self.lib.vl_apgd_scratch_bytes(self.h, int(batch), int(steps), C.byref(n)), "vl_apgd_scratch_bytes")
         return n.value
 
-    def _apgd_scratch(self, batch: int, steps: int):
-        """The attack's image state (about 6 image batches) as one tensor cached per (batch, steps): the same address on every
-        call, so the captured iteration is reused."""
-        cache = self.__dict__.setdefault("_apgd_scratch_cache", {})
-        key = (int(batch), int(steps))
+    def _attack_scratch(self, name: str, key, nbytes_fn):
+        """An attack's state (APGD: about 6 image batches at `key` = (batch, steps); Square: three and the trace at (batch,
+        n_queries)) as one tensor cached per attack `name` and key: the same address on every call, so the captured iteration is
+        reused.  Returns (tensor, 256-byte aligned base pointer, bytes)."""
+        cache = self.__dict__.setdefault(f"_{name}_scratch_cache", {})
+        key = tuple(int(k) for k in key)
         if key not in cache:
-            while len(cache) >= 2:                 # a full batch and a ragged last one; 1.1 GB each at batch 256
+            while len(cache) >= 2:                 # a full batch and a ragged last one; APGD: 1.1 GB each at batch 256
                 cache.pop(next(iter(cache)))
-            n = self.apgd_scratch_bytes(batch, steps)
+            n = nbytes_fn(*key)
             buf = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
             cache[key] = (buf, (buf.data_ptr() + 255) // 256 * 256, n)
         else:
@@ -323,7 +324,7 @@ class Engine:
         B, steps = x0.shape[0], int(steps)
         self.plan(B, False)
         if scratch is None:
-            _, base, nbytes = self._apgd_scratch(B, steps)
+            _, base, nbytes = self._attack_scratch("apgd", (B, steps), self.apgd_scratch_bytes)
         else:
             base, nbytes = scratch
         xi = self._check_images(x_init) if x_init is not None else None
@@ -380,21 +381,6 @@ class Engine:
         check(self.lib.vl_square_scratch_bytes(self.h, int(batch), int(n_queries), C.byref(n)), "vl_square_scratch_bytes")
         return n.value
 
-    def _square_scratch(self, batch: int, n_queries: int):
-        """The attack's state (three image batches and the trace) as one tensor cached per (batch, n_queries): the same address
-        on every call, so the captured iteration is reused."""
-        cache = self.__dict__.setdefault("_square_scratch_cache", {})
-        key = (int(batch), int(n_queries))
-        if key not in cache:
-            while len(cache) >= 2:                 # a full batch and a ragged last one
-                cache.pop(next(iter(cache)))
-            n = self.square_scratch_bytes(batch, n_queries)
-            buf = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
-            cache[key] = (buf, (buf.data_ptr() + 255) // 256 * 256, n)
-        else:
-            cache[key] = cache.pop(key)            # most recently used last
-        return cache[key]
-
     def square_attack(self, x0: torch.Tensor, labels: torch.Tensor, eps, n_queries=5000, p_init=0.8, seed=0, image_offset=0,
                       check_every=0, trace=False, scratch=None, first=0, count=None) -> Dict[str, torch.Tensor]:
         """vl_square_attack.  Returns {"x_best", "margin_min" [B], "queries" [B] int32, "robust" [B] bool, "replays": how many
@@ -408,7 +394,7 @@ class Engine:
         B, N = x0.shape[0], int(n_queries)
         self.plan(B, False)
         if scratch is None:
-            _, base, nbytes = self._square_scratch(B, N)
+            _, base, nbytes = self._attack_scratch("square", (B, N), self.square_scratch_bytes)
         else:
             base, nbytes = scratch
         out = {"x_best": torch.empty_like(x0), "margin_min": torch.empty(B, dtype=torch.float32, device=self.device),

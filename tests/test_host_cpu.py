@@ -312,8 +312,9 @@ def test_integration_md_indexes_every_abi_symbol():
 def test_integration_md_lists_every_environment_switch_and_csrc_reads_them_one_way():
     """INTEGRATION.md section 5 has one table row per VITLORA_* name that the library sources, the package's Python modules and the
     command-line scripts mention, and no row for a name none of them mentions; in csrc/ a switch is read through env.h
-    (env_int / env_double / env_flag) -- the only other getenv calls are the three named helpers of vitlora.hip whose values
-    are neither a flag nor an integer (VITLORA_RESID, VITLORA_ATTN_IMG, VITLORA_GRAPH_DUMP)."""
+    (env_int / env_double / env_flag) -- the only other getenv calls are the three named helpers whose values are neither a
+    flag nor an integer (VITLORA_RESID, VITLORA_ATTN_IMG: env_resid / env_attn_img of vitlora.hip; VITLORA_GRAPH_DUMP:
+    env_graph_dump of vit_attacks.hip)."""
     import glob
     csrc = os.path.join(ROOT, PKG, "csrc")
     native = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
