@@ -16,9 +16,10 @@ from ._lib import LIB_PATH, NonFiniteGradient, VitLoraError, check  # noqa: F401
 from .engine import (IMAGENET_MEAN, IMAGENET_STD, ArchConfig, Engine, LoraSpec,  # noqa: F401
                      apgd_schedule, canonical_key, expected_keys, resolve_targets)
 
-# APGD, Square, AutoAttack (auto_attack.py:98-108) and the other facade names resolve lazily from .attacks / .model / ... below
+# APGD, APGDT, Square, AutoAttack, run_suite (auto_attack.py:98-108) and the other facade names resolve lazily from .attacks / .model / ... below
 __all__ = ["ArchConfig", "Engine", "LoraSpec", "VitLoraError", "NonFiniteGradient", "LIB_PATH", "IMAGENET_MEAN", "IMAGENET_STD",
-           "resolve_targets", "canonical_key", "expected_keys", "apgd_schedule", "APGD", "Square", "AutoAttack"]
+           "resolve_targets", "canonical_key", "expected_keys", "apgd_schedule", "APGD", "APGDT", "Square", "AutoAttack",
+           "run_suite"]
 
 
 def __getattr__(name):

@@ -150,6 +150,28 @@ SIGNATURES.update({
 })
 
 
+class VLApgdtArgs(C.Structure):
+    """vl_apgdt_args of include/vitlora.h (field for field)."""
+    _fields_ = [
+        ("x0", C.c_void_p), ("labels", C.c_void_p), ("batch", C.c_int32), ("steps", C.c_int32),
+        ("eps", C.c_float), ("rho", C.c_float), ("n_target_classes", C.c_int32), ("n_restarts", C.c_int32),
+        ("seed", C.c_uint64), ("targets_in", C.c_void_p),
+        ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t),
+        ("x_adv", C.c_void_p), ("robust", C.c_void_p), ("clean_correct", C.c_void_p), ("targets", C.c_void_p),
+        ("fooled_by", C.c_void_p), ("loss_best", C.c_void_p), ("robust_run", C.c_void_p),
+        ("trace_loss", C.c_void_p), ("trace_step", C.c_void_p), ("trace_pred", C.c_void_p),
+        ("stream", C.c_void_p), ("reserved", C.c_int32 * 4),
+    ]
+
+
+SIGNATURES.update({
+    "vl_apgdt_scratch_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "vl_apgdt_attack": (C.c_int, [C.c_void_p, C.POINTER(VLApgdtArgs)]),
+    "vl_dlr_targeted_loss": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 4),
+    "vl_apgd_targets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+})
+
+
 class VLSquareArgs(C.Structure):
     """vl_square_args of include/vitlora.h (field for field)."""
     _fields_ = [

@@ -7,6 +7,11 @@
 All arithmetic runs in the HIP library: the forward/backward chain, the fused sign/project
 step (vl_pgd_step), the random start (vl_pgd_init) and the whole PGD loop as one hipGraph per
 iteration (vl_pgd_attack).
+
+    APGD / APGDT / Square (torchattacks' signatures), AutoAttack (autoattack's, auto_attack.py:98-108) and run_suite: the built
+    components of AutoAttack's standard L-inf suite -- APGD-CE (vl_apgd_attack), APGD-T (vl_apgdt_attack) and Square
+    (vl_square_attack), each a device-resident loop.  FAB-T is not built.  The AutoAttack class itself still accepts only
+    'apgd-ce' and 'square' (its refusals are pinned by tests); APGD-T is reached through APGDT and run_suite.
 """
 from __future__ import annotations
 
@@ -169,6 +174,46 @@ class APGD(_Attack):
         return self._finish(eng, adv)
 
 
+def _apgd_t(eng, x, labels, eps, steps, rho, n_target_classes, n_restarts, seed):
+    """APGD-T on [0,1] images (the engine's normalisation is the caller's to set): every target class and restart and the fold
+    over them run inside one library call (vl_apgdt_attack).  n_target_classes is capped by num_labels - 1.  Returns
+    (adv, still_robust [B] bool, clean_correct [B] bool, the call's result dict)."""
+    labels = labels.to(device=eng.device, dtype=torch.int64)
+    k = max(1, min(int(n_target_classes), eng.arch.num_labels - 1))
+    res = eng.apgdt_attack(x, labels, eps, steps, rho=rho, n_target_classes=k, n_restarts=max(1, int(n_restarts)), seed=int(seed))
+    return res["x_adv"], res["robust"], res["clean_correct"], res
+
+
+class APGDT(_Attack):
+    """torchattacks.APGDT(model, norm='Linf', eps, steps, n_restarts, seed, eot_iter, rho, n_classes): targeted Auto-PGD on the DLR
+    loss towards each of the n_target_classes = min(9, n_classes - 1) (capped by the model's num_labels - 1) most likely wrong
+    classes, every run and the fold over runs on the device (vl_apgdt_attack).  An image counts as fooled when it is
+    misclassified; hitting the target is not required.  Run k * n_restarts + r uses the library's counter-based random start with
+    seed + that index.  The algorithm is the library's restatement of the autoattack package (include/vitlora.h, DESIGN.md section
+    3.11): parity with the package is unpinned.  After a call `last` holds the result dict of Engine.apgdt_attack."""
+
+    def __init__(self, model, norm="Linf", eps=8 / 255, steps=10, n_restarts=1, seed=0, eot_iter=1, rho=0.75, n_classes=10):
+        super().__init__(model)
+        if norm != "Linf":
+            raise ValueError(f"APGDT: only norm='Linf' is built (got {norm!r})")
+        if eot_iter != 1:
+            raise ValueError(f"APGDT: only eot_iter=1 is built (got {eot_iter!r})")
+        self.norm, self.eps, self.steps, self.n_restarts, self.seed, self.eot_iter, self.rho = norm, eps, steps, n_restarts, seed, eot_iter, rho
+        self.n_classes = n_classes
+        self.n_target_classes = min(9, int(n_classes) - 1)
+        self.last = None
+
+    def forward(self, images, labels):
+        vit, eng, x = self._prepare(images)
+        if self._norm is None:
+            eng.set_normalization([0.0, 0.0, 0.0], [1.0, 1.0, 1.0])
+        adv, _, _, self.last = _apgd_t(eng, x, labels, self.eps, self.steps, self.rho, self.n_target_classes, self.n_restarts, self.seed)
+        if self._norm is None:
+            from .engine import IMAGENET_MEAN, IMAGENET_STD
+            eng.set_normalization(IMAGENET_MEAN, IMAGENET_STD)   # back to the library default
+        return self._finish(eng, adv.clone())                    # (_finish normalises in place: `last` keeps the [0,1] point)
+
+
 def _square(eng, x, labels, eps, n_queries, p_init, n_restarts, seed, image_offset=0, check_every=0):
     """Square with restarts on [0,1] images (the engine's normalisation is the caller's to set): an image that is classified
     correctly before the attack takes x_best of the first restart that fools it (restart r uses seed + r).  Returns
@@ -222,9 +267,10 @@ class Square(_Attack):
 
 class AutoAttack:
     """autoattack.AutoAttack(model, norm='Linf', eps, version, attacks_to_run, seed) as auto_attack.py:98-108 uses it.
-    Of the standard suite (APGD-CE, APGD-T, FAB-T, Square) the first and the last component are built: version='custom' runs any
-    non-empty ordered subset of ['apgd-ce', 'square'], each component's result taken only for the images that are still robust;
-    version='standard' raises NotImplementedError (APGD-T and FAB-T are missing).  Images are in [0,1]; the model is fed
+    Of the standard suite (APGD-CE, APGD-T, FAB-T, Square) this class runs the first and the last component: version='custom' runs
+    any non-empty ordered subset of ['apgd-ce', 'square'], each component's result taken only for the images that are still robust;
+    version='standard' raises NotImplementedError (FAB-T is not built; APGD-T is, and runs through run_suite below, which this
+    class calls -- accepting 'apgd-t' here is a follow-up that goes with the tests that pin this class's refusals).  Images are in [0,1]; the model is fed
     (x - mean) / std (the reference wraps its model in a NormalizedModel, auto_attack.py:47-55), ImageNet constants unless
     `mean` / `std` are given.  Square draws per image from (seed, index of the image in x_orig): its result does not depend on bs."""
 
@@ -255,32 +301,57 @@ class AutoAttack:
 
     def run_standard_evaluation(self, x_orig, y_orig, bs=250, image_offset=0):
         """image_offset: the index of x_orig[0] in the data set when a caller feeds the set in several calls (Square only)."""
-        vit = _unwrap(self.model)
-        eng = vit._engine()
-        vit.sync_params()
-        eng.set_normalization(self.mean, self.std)
-        x_all = x_orig.detach().to(device=eng.device, dtype=torch.float32).contiguous()
-        y_all = y_orig.to(device=eng.device, dtype=torch.int64)
-        out, n_robust = [], 0
-        for lo in range(0, x_all.shape[0], int(bs)):
-            x, y = x_all[lo:lo + bs], y_all[lo:lo + bs]
-            adv = robust = None
-            for name in self.attacks_to_run:
-                if name == "apgd-ce":
-                    a, r, _, _ = _apgd_ce(eng, x, y, self.eps, self.steps, self.rho, self.n_restarts, self.seed)
-                else:
-                    a, r, _, _ = _square(eng, x, y, self.eps, self.square_queries, self.p_init, self.n_restarts, self.seed,
-                                         image_offset=int(image_offset) + lo, check_every=self.check_every)
-                if adv is None:
-                    adv, robust = a, r
-                else:             # only for the images the earlier components left robust (r is False for clean-wrong images too)
-                    take = robust & ~r
-                    adv = torch.where(take.view(-1, 1, 1, 1), a, adv)
-                    robust = robust & r
-            out.append(adv)
-            n_robust += int(robust.sum().item())
-        self.robust_accuracy = n_robust / max(1, x_all.shape[0])
-        return torch.cat(out)
+        adv, self.robust_accuracy = run_suite(self.model, x_orig, y_orig, self.eps, attacks=self.attacks_to_run, bs=bs, seed=self.seed,
+                                              steps=self.steps, n_restarts=self.n_restarts, rho=self.rho,
+                                              square_queries=self.square_queries, p_init=self.p_init, check_every=self.check_every,
+                                              mean=self.mean, std=self.std, image_offset=image_offset)
+        return adv
 
 
-__all__ = ["batched_fgsm_attack", "FGSM", "PGD", "APGD", "Square", "AutoAttack", "LogitsModel"]
+def run_suite(model, x, y, eps, attacks=("apgd-ce", "apgd-t", "square"), bs=250, seed=0, steps=100, n_restarts=1, rho=0.75,
+              n_target_classes=9, square_queries=5000, p_init=0.8, check_every=0, mean=None, std=None, image_offset=0):
+    """The components of AutoAttack's standard L-inf suite that are built -- 'apgd-ce', 'apgd-t', 'square' -- in the order given,
+    on images in [0,1] with the model fed (x - mean) / std (ImageNet constants unless given), in batches of `bs`.  Each component's
+    result is taken only for the images the earlier components left robust.  'fab-t' raises NotImplementedError (not built).
+    n_target_classes is capped by the model's num_labels - 1.  image_offset: the index of x[0] in the data set (Square draws per
+    image index).  Returns (x_adv, robust_accuracy)."""
+    run = list(attacks)
+    for name in run:
+        if name == "fab-t":
+            raise NotImplementedError("run_suite: 'fab-t' is not built")
+        if name not in ("apgd-ce", "apgd-t", "square"):
+            raise ValueError(f"run_suite: unknown attack {name!r}")
+    if not run or len(set(run)) != len(run):
+        raise ValueError("run_suite: attacks must be a non-empty list without repeats")
+    vit = _unwrap(model)
+    eng = vit._engine()
+    vit.sync_params()
+    from .engine import IMAGENET_MEAN, IMAGENET_STD
+    eng.set_normalization([float(v) for v in (mean if mean is not None else IMAGENET_MEAN)],
+                          [float(v) for v in (std if std is not None else IMAGENET_STD)])
+    x_all = x.detach().to(device=eng.device, dtype=torch.float32).contiguous()
+    y_all = y.to(device=eng.device, dtype=torch.int64)
+    out, n_robust = [], 0
+    for lo in range(0, x_all.shape[0], int(bs)):
+        xb, yb = x_all[lo:lo + bs], y_all[lo:lo + bs]
+        adv = robust = None
+        for name in run:
+            if name == "apgd-ce":
+                a, r, _, _ = _apgd_ce(eng, xb, yb, eps, steps, rho, n_restarts, seed)
+            elif name == "apgd-t":
+                a, r, _, _ = _apgd_t(eng, xb, yb, eps, steps, rho, n_target_classes, n_restarts, seed)
+            else:
+                a, r, _, _ = _square(eng, xb, yb, eps, square_queries, p_init, n_restarts, seed,
+                                     image_offset=int(image_offset) + lo, check_every=check_every)
+            if adv is None:
+                adv, robust = a, r
+            else:             # only for the images the earlier components left robust (r is False for clean-wrong images too)
+                take = robust & ~r
+                adv = torch.where(take.view(-1, 1, 1, 1), a, adv)
+                robust = robust & r
+        out.append(adv)
+        n_robust += int(robust.sum().item())
+    return torch.cat(out), n_robust / max(1, x_all.shape[0])
+
+
+__all__ = ["batched_fgsm_attack", "FGSM", "PGD", "APGD", "APGDT", "Square", "AutoAttack", "run_suite", "LogitsModel"]

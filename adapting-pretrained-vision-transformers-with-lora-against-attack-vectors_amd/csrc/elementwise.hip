@@ -975,6 +975,134 @@ __global__ __launch_bounds__(256) void apgd_step_kernel(float* __restrict__ x_ad
 }
 
 // ---------------------------------------------------------------------------------
+// APGD-T (targeted Auto-PGD on the DLR loss; DESIGN.md section 3.11 -- a restatement of the autoattack package's
+// APGDAttack_targeted from memory: parity with the package is UNPINNED).  The iteration is APGD's with another loss kernel;
+// apgd_track_kernel and apgd_step_kernel are reused unchanged ("fooled" stays argmax != label).
+// ---------------------------------------------------------------------------------
+// The wave's best (value, index) in the order "value descending, index ascending"; NO_IDX marks "no candidate".  Every lane
+// returns lane 0's result, so the lanes agree even on a row that holds NaN.
+constexpr int NO_IDX = 0x7fffffff;
+__device__ __forceinline__ bool ranks_before(float v, int c, float bv, int bc) {
+    return c != NO_IDX && (bc == NO_IDX || v > bv || (v == bv && c < bc));
+}
+__device__ __forceinline__ void wave_best(float& v, int& c) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(v, o, 64);
+        const int oc = __shfl_xor(c, o, 64);
+        if (ranks_before(ov, oc, v, c)) { v = ov; c = oc; }
+    }
+    v = __shfl(v, 0, 64);
+    c = __shfl(c, 0, 64);
+}
+
+// DLR-targeted loss, one wave per image (four per block), any C >= 4: pi1 .. pi4 by four wave arg-max passes, each over the
+// classes that rank strictly after the previous pick.  N = z_y - z_t, D = (z_pi1 - (z_pi3 + z_pi4) / 2) + 1e-12, q = N / D,
+// loss = -q, and the row written is  D * dloss/dz = -[(d_cy - d_ct) - q (d_c,pi1 - d_c,pi3 / 2 - d_c,pi4 / 2)]:
+// the positive per-image factor D is DELIBERATE -- only the sign of the input gradient is used and the backward rescales each
+// image anyway (grad_scale_kernel); without it a near-tie among the top four classes puts 1 / D^2, about 1e24, into the row.
+// Every operation is rounded on its own, in this order (no FMA contraction: the float32 restatement in tests/apgdt_ref.py is
+// bit-exact).  A label outside [0, C): NaN row, NaN loss, *err = 1 (as ce_loss_kernel); a target outside [0, C) or equal to the
+// label: the same with *err = 6.
+__global__ __launch_bounds__(256) void dlr_targeted_loss_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                                const int32_t* __restrict__ targets, int B, int C,
+                                                                float* __restrict__ dlogits, float* __restrict__ loss_img,
+                                                                int* __restrict__ err) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int64_t yl = labels[b];
+    const int t = targets[b];
+    const bool bad_label = yl < 0 || yl >= C, bad_target = t < 0 || t >= C || (int64_t)t == yl;
+    if (bad_label || bad_target) {
+        for (int c = lane; c < C; c += 64) dlogits[(int64_t)b * C + c] = __builtin_nanf("");
+        if (lane == 0) { loss_img[b] = __builtin_nanf(""); if (err) *err = bad_label ? 1 : 6; }
+        return;
+    }
+    const int y = (int)yl;
+    const float* lr = logits + (int64_t)b * C;
+    float pv[4];
+    int pc[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float bv = 0.f;
+        int bc = NO_IDX;
+        for (int c = lane; c < C; c += 64) {
+            const float v = lr[c];
+            const bool after = k == 0 || ranks_before(pv[k ? k - 1 : 0], pc[k ? k - 1 : 0], v, c);      // strictly after the previous pick
+            if (after && ranks_before(v, c, bv, bc)) { bv = v; bc = c; }
+        }
+        wave_best(bv, bc);
+        if (bc == NO_IDX) { bv = k ? pv[k ? k - 1 : 0] : 0.f; bc = k ? pc[k ? k - 1 : 0] : 0; }      // only on a row that holds NaN: stay inside the row
+        pv[k] = bv; pc[k] = bc;
+    }
+    const float n = lr[y] - lr[t];
+    const float h = (pv[2] + pv[3]) * 0.5f;
+    const float d = (pv[0] - h) + 1e-12f;
+    const float q = n / d;
+    for (int c = lane; c < C; c += 64) {
+        const float a = (c == y ? 1.f : 0.f) - (c == t ? 1.f : 0.f);
+        const float w = ((c == pc[0] ? 1.f : 0.f) - (c == pc[2] ? 0.5f : 0.f)) - (c == pc[3] ? 0.5f : 0.f);
+        dlogits[(int64_t)b * C + c] = -(a - q * w);
+    }
+    if (lane == 0) loss_img[b] = -q;
+}
+
+// Target classes of APGD-T, one wave per image (four per block): clean_correct = (first maximum == label), then n_target times
+// the arg-max over the classes != label that rank strictly after the previous pick (value descending, index ascending).
+// n_target <= C - 1, so every pick exists unless the row holds NaN (then -1, which the loss kernel refuses).
+__global__ __launch_bounds__(256) void apgd_targets_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                           int B, int C, int n_target, int32_t* __restrict__ targets,
+                                                           int32_t* __restrict__ clean_correct) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int64_t yl = labels[b];
+    const float* lr = logits + (int64_t)b * C;
+    float pv = 0.f;
+    int pc = NO_IDX;
+    for (int c = lane; c < C; c += 64) { const float v = lr[c]; if (ranks_before(v, c, pv, pc)) { pv = v; pc = c; } }
+    wave_best(pv, pc);
+    if (lane == 0) clean_correct[b] = ((int64_t)pc == yl) ? 1 : 0;
+    pc = NO_IDX;
+    for (int k = 0; k < n_target; ++k) {
+        float bv = 0.f;
+        int bc = NO_IDX;
+        for (int c = lane; c < C; c += 64) {
+            const float v = lr[c];
+            const bool after = pc == NO_IDX || ranks_before(pv, pc, v, c);
+            if ((int64_t)c != yl && after && ranks_before(v, c, bv, bc)) { bv = v; bc = c; }
+        }
+        wave_best(bv, bc);
+        if (lane == 0) targets[(int64_t)k * B + b] = bc == NO_IDX ? -1 : bc;
+        if (bc == NO_IDX) { for (int j = k + 1; j < n_target; ++j) if (lane == 0) targets[(int64_t)j * B + b] = -1; return; }
+        pv = bv; pc = bc;
+    }
+}
+
+// The fold over runs: blockIdx.y = image, so the branch is uniform over the block.  An image that was still robust and that this
+// run fooled takes the run's misclassified point (16-byte copies) and records the run; still_out = still_in & run_robust.  still_in
+// and still_out are two arrays, so no block reads a word that another block writes.
+__global__ __launch_bounds__(256) void apgdt_fold_kernel(float* __restrict__ x_out, const float* __restrict__ x_best_adv,
+                                                         const int32_t* __restrict__ still_in, int32_t* __restrict__ still_out,
+                                                         const int32_t* __restrict__ run_robust, int32_t* __restrict__ fooled_by,
+                                                         int run, int64_t n4) {
+    const int b = blockIdx.y;
+    const bool still = still_in[b] != 0, rob = run_robust[b] != 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        still_out[b] = (still && rob) ? 1 : 0;
+        if (still && !rob) fooled_by[b] = run;
+    }
+    if (!still || rob) return;
+    const int64_t base = (int64_t)b * n4;
+    const f32x4* const src = (const f32x4*)x_best_adv + base;
+    f32x4* const dst = (f32x4*)x_out + base;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += stride) dst[i] = src[i];
+}
+
+// ---------------------------------------------------------------------------------
 // Square attack (Andriushchenko et al. 2020; L-inf, untargeted margin loss, rescaled schedule).  The algorithm is the restatement
 // in DESIGN.md section 3.10 -- written from memory of the autoattack package's square.py and the paper, neither installed here:
 // parity with the package is UNPINNED.  Two deliberate deviations: the window and its signs are drawn PER IMAGE (an image's
@@ -1483,6 +1611,22 @@ void k_apgd_step(float* x_adv, float* x_old, float* x_best, float* x_best_adv, f
     const int per_img = nblk((n4 + 1) / 2, 256, std::max(1, 8192 / B));
     hipLaunchKernelGGL(apgd_step_kernel, dim3(per_img, B), dim3(256), 0, s, x_adv, x_old, x_best, x_best_adv, grad_best, x0, grad,
                        flags, step, n4, eps, sched, ctr, N, a, last, err);
+}
+void k_dlr_targeted_loss(const float* logits, const int64_t* labels, const int32_t* targets, int B, int C, float* dlogits,
+                         float* loss_img, float* loss, int* err, hipStream_t s) {
+    hipLaunchKernelGGL(dlr_targeted_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, s, logits, labels, targets, B, C, dlogits, loss_img, err);
+    if (loss) hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(256), 0, s, loss_img, B, loss);
+}
+void k_apgd_targets(const float* logits, const int64_t* labels, int B, int C, int n_target, int32_t* targets,
+                    int32_t* clean_correct, hipStream_t s) {
+    hipLaunchKernelGGL(apgd_targets_kernel, dim3((B + 3) / 4), dim3(256), 0, s, logits, labels, B, C, n_target, targets, clean_correct);
+}
+void k_apgdt_fold(float* x_out, const float* x_best_adv, const int32_t* still_in, int32_t* still_out, const int32_t* run_robust,
+                  int32_t* fooled_by, int run, int B, int64_t n_img, hipStream_t s) {
+    ProfScope prof_("apgdt_fold_kernel", 0.0, (double)B * n_img * 8.0, s);
+    const int64_t n4 = n_img / 4;                    // n_img % 4 == 0 is the caller's to check
+    hipLaunchKernelGGL(apgdt_fold_kernel, dim3(nblk(n4, 256, std::max(1, 8192 / B)), B), dim3(256), 0, s, x_out, x_best_adv, still_in,
+                       still_out, run_robust, fooled_by, run, n4);
 }
 // p = p_init / 2^k for the k thresholds that it = int((j - 1) / N * 10000) exceeds strictly; side = round-half-even(sqrt(p S S)),
 // all in double (p_init enters as the float the ABI carries).  from[k] = the first proposal that uses side[k], N + 1 if none.

@@ -78,6 +78,23 @@ void k_apgd_track(const ApgdState& st, const float* loss_img, const float* logit
 void k_apgd_step(float* x_adv, float* x_old, float* x_best, float* x_best_adv, float* grad_best, const float* x0,
                  const float* grad, const uint32_t* flags, const float* step, int B, int64_t n_img, float eps,
                  const ApgdSched* sched, int32_t* ctr, int N, float a, int last, hipStream_t s, int* err = nullptr);
+// ---- APGD-T (targeted Auto-PGD on the DLR loss): elementwise.hip ----
+// DLR-targeted loss of one row: pi = the row's descending order (value descending, index ascending), N = z_y - z_t,
+// D = z_pi1 - (z_pi3 + z_pi4) / 2 + 1e-12, loss = -N / D (maximised).  dlogits = D * dloss/dz, NOT dloss/dz: only the sign of the
+// input gradient is used and the backward rescales every image anyway (k_grad_scale), while dloss/dz itself carries 1 / D^2 --
+// about 1e24 at a near-tie among the top four classes.  C >= 4.  err (optional): set to 1 for a label outside [0, C), to 6 for a
+// target outside [0, C) or equal to the label; that image's loss and dlogits row become NaN.  loss (optional): the batch mean.
+void k_dlr_targeted_loss(const float* logits, const int64_t* labels, const int32_t* targets, int B, int C, float* dlogits,
+                         float* loss_img, float* loss, int* err, hipStream_t s);
+// targets[k * B + b] = the class with the (k + 1)-th largest logit among the classes != labels[b] (ties: the lower index first),
+// k < n_target <= C - 1; clean_correct[b] = (argmax == labels[b], the first maximum)
+void k_apgd_targets(const float* logits, const int64_t* labels, int B, int C, int n_target, int32_t* targets,
+                    int32_t* clean_correct, hipStream_t s);
+// The fold over runs: for an image with still_in[b] && !run_robust[b], x_out[b] <- x_best_adv[b] and fooled_by[b] = run;
+// still_out[b] = still_in[b] & run_robust[b].  still_in and still_out are two arrays (no block reads a word another one writes).
+// n_img % 4 == 0.
+void k_apgdt_fold(float* x_out, const float* x_best_adv, const int32_t* still_in, int32_t* still_out, const int32_t* run_robust,
+                  int32_t* fooled_by, int run, int B, int64_t n_img, hipStream_t s);
 // ---- Square attack (score-based random search, L-inf): elementwise.hip ----
 // Replay j of the captured iteration evaluates proposal j (replay 0: the stripes) and draws proposal j + 1.
 enum { SQ_PREV = 1u, SQ_ACCEPT = 2u, SQ_NEXT = 4u };      // per-image flag word of one replay: a pending window to resolve

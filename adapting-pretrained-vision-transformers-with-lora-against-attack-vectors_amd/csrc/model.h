@@ -97,8 +97,9 @@ struct Pass {
 // Cache of captured attack iterations (vit_attacks.hip).  The key is everything an iteration bakes in besides the handle's options
 // (a changed option drops the whole cache: drop_graphs); fields a kind does not use stay 0 / nullptr.  PGD: B, chains, eps, alpha
 // (its staging buffers live in the workspace).  APGD: B, steps, eps, rho and the caller's scratch, which its kernels read.
-// Square: B, steps (n_queries), eps, scratch.
-enum { GRAPH_PGD = 0, GRAPH_APGD = 1, GRAPH_SQUARE = 2 };
+// Square: B, steps (n_queries), eps, scratch.  APGD-T: as APGD (the target row it reads sits at a fixed place in the scratch, so
+// one entry serves every target and restart).
+enum { GRAPH_PGD = 0, GRAPH_APGD = 1, GRAPH_SQUARE = 2, GRAPH_APGDT = 3 };
 struct GraphKey {
     int kind, B, chains, steps; float eps, alpha, rho; const void* scratch;
     bool operator==(const GraphKey& o) const {

@@ -1,4 +1,4 @@
-// The attacks on the ViT handle (include/vitlora.h): PGD, Auto-PGD (APGD-CE) and Square, each a device-resident loop whose one
+// The attacks on the ViT handle (include/vitlora.h): PGD, Auto-PGD (APGD-CE, APGD-T) and Square, each a device-resident loop whose one
 // iteration is captured once as a hipGraph and replayed.  This file holds the ONE cache of those graphs (GraphKey / GraphEntry:
 // model.h), the one capture sequence, the one rule for "eager or replay", the attacks' scratch layouts and their entry points.
 // Forward, backward and the workspace are vitlora.hip's (helpers declared in model.h); all arithmetic is in the kernel files.
@@ -214,6 +214,42 @@ int apgd_iteration(vl_model* m, const ApgdLayout& L, int B, int N, float eps, fl
     return VL_OK;
 }
 
+// ---- APGD-T (targeted Auto-PGD on the DLR loss, L-inf; include/vitlora.h) ----
+// APGD's layout first (so target_cur, which the captured iteration reads, sits at a place that does not depend on the number of
+// targets), then the fold's state and the target table.
+struct ApgdtLayout {
+    ApgdLayout a;
+    int32_t *target_cur, *still[2], *clean_correct, *fooled_by, *targets;
+    float* x_out;
+};
+size_t apgdt_carve(const vl_model* m, int B, int N, int n_target, char* base, ApgdtLayout& L) {
+    Carver cv{base, apgd_carve(m, B, N, base, L.a)};
+    const size_t img = (size_t)B * 3 * m->S * m->S * 4, row = (size_t)B * 4;
+    L.target_cur = cv.take<int32_t>(row);
+    L.still[0] = cv.take<int32_t>(row); L.still[1] = cv.take<int32_t>(row);
+    L.clean_correct = cv.take<int32_t>(row); L.fooled_by = cv.take<int32_t>(row);
+    L.x_out = cv.take<float>(img);
+    L.targets = cv.take<int32_t>((size_t)n_target * row);
+    return cv.off;
+}
+// the shared scratch check sizes APGD's part (batch, steps); the whole size is checked by the caller, which knows n_target
+size_t apgdt_bytes_min(const vl_model* m, int batch, int steps) { ApgdtLayout sz; return apgdt_carve(m, batch, steps, 1, nullptr, sz); }
+const ScratchSpec kApgdtScratch = {"APGD-T", "steps", "vl_apgdt_scratch_bytes", apgdt_bytes_min};
+
+// one APGD-T iteration in the main pass: APGD's with the DLR-targeted loss towards target_cur
+int apgdt_iteration(vl_model* m, const ApgdtLayout& L, int B, int N, float eps, float rho, hipStream_t s) {
+    Pass& p = m->main;
+    int rc = forward_impl(m, p, L.a.x_adv, B, 1, 0, s);
+    if (rc) return rc;
+    k_dlr_targeted_loss(p.ws.logits, L.a.labels, L.target_cur, B, m->C, p.ws.dlogits, p.ws.loss_img, p.ws.loss, m->err_flag, s);
+    p.have_loss = 1;
+    if ((rc = backward_impl(m, p, p.ws.grad_img, nullptr, s))) return rc;
+    k_apgd_track(L.a.st, p.ws.loss_img, p.ws.logits, L.a.labels, B, m->C, N, eps, rho, s);
+    k_apgd_step(L.a.x_adv, L.a.x_old, L.a.x_best, L.a.x_best_adv, L.a.grad_best, L.a.x0, p.ws.grad_img, L.a.st.flags, L.a.st.step, B,
+                (int64_t)3 * m->S * m->S, eps, L.a.st.sched, L.a.st.ctr, N, 0.f, 0, s, m->err_flag);
+    return VL_OK;
+}
+
 // ---- Square attack (L-inf, margin loss; include/vitlora.h) -------------
 // Everything the attack keeps between replays, carved from the caller's scratch (base == nullptr: size only).
 struct SquareLayout {
@@ -379,7 +415,86 @@ int vl_debug_apgd_track(vl_model* m, const vl_apgd_track_case* c, void* stream) 
     return VL_OK;
 }
 
+int vl_apgdt_scratch_bytes(vl_model* m, int batch, int steps, int n_target_classes, size_t* bytes) {
+    if (!m || !bytes || batch <= 0 || steps < 1 || steps > 65535 || n_target_classes < 1 || n_target_classes > 65535)
+        return fail(VL_ERR_ARG, "bad argument");
+    ApgdtLayout sz;
+    *bytes = apgdt_carve(m, batch, steps, n_target_classes, nullptr, sz);
+    return VL_OK;
+}
+
+int vl_apgdt_attack(vl_model* m, const vl_apgdt_args* a) {
+    if (!m || !a || !a->x0 || !a->labels) return fail(VL_ERR_ARG, "bad argument");
+    if (m->C < 4) return fail(VL_ERR_UNSUPPORTED, "the DLR loss needs num_labels >= 4");
+    if (a->n_target_classes < 1 || a->n_target_classes > m->C - 1) return fail(VL_ERR_ARG, "n_target_classes must be 1 .. num_labels - 1");
+    if (a->n_restarts < 1) return fail(VL_ERR_ARG, "n_restarts must be >= 1");
+    if (!(a->eps >= 0.f) || !(a->eps < INFINITY) || !(a->rho >= 0.f) || !(a->rho <= 1.f)) return fail(VL_ERR_ARG, "eps must be finite and >= 0, rho in [0, 1]");
+    int rc = check_attack_scratch(m, kApgdtScratch, a->scratch, a->scratch_bytes, a->batch, a->steps);
+    if (rc) return rc;
+    const int B = a->batch, N = a->steps, K = a->n_target_classes, R = a->n_restarts;
+    ApgdtLayout L;
+    const size_t need = apgdt_carve(m, B, N, K, (char*)a->scratch, L);
+    if (a->scratch_bytes < need) return fail(VL_ERR_ARG, "APGD-T scratch too small: %zu < %zu (vl_apgdt_scratch_bytes)", a->scratch_bytes, need);
+    hipStream_t s = (hipStream_t)a->stream;
+    if ((rc = check_async(m))) return rc;
+    if (m->dirty && (rc = vl_lora_commit(m, a->stream))) return rc;     // the attack sees the CURRENT adapters
+    const float eps = a->eps, rho = a->rho;
+    const int64_t n_img = (int64_t)3 * m->S * m->S, n = (int64_t)B * n_img;
+    const size_t row = (size_t)B * 4;
+    // staging, as vl_apgd_attack: the captured iteration only ever sees addresses inside the scratch and the workspace
+    HIPCHK(hipMemcpyAsync(L.a.x0, a->x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(L.a.labels, a->labels, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(L.x_out, L.a.x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    // the clean pass: clean_correct and the target table
+    m->fwd_chains = 0;
+    if ((rc = forward_impl(m, m->main, L.a.x0, B, 1, 0, s))) return rc;
+    k_apgd_targets(m->main.ws.logits, L.a.labels, B, m->C, K, L.targets, L.clean_correct, s);
+    if (a->targets_in) HIPCHK(hipMemcpyAsync(L.targets, a->targets_in, (size_t)K * row, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(L.still[0], L.clean_correct, row, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemsetAsync(L.fooled_by, 0xFF, row, s));                  // -1
+    const GraphKey key = {GRAPH_APGDT, B, 1, N, eps, 0.f, rho, a->scratch};
+    int run = 0;
+    for (int k = 0; k < K; ++k) {
+        HIPCHK(hipMemcpyAsync(L.target_cur, L.targets + (size_t)k * B, row, hipMemcpyDeviceToDevice, s));
+        for (int r = 0; r < R; ++r, ++run) {
+            k_apgd_rand_init(L.a.x_adv, L.a.x0, eps, a->seed + (uint64_t)run, B, n_img, s);
+            HIPCHK(hipMemcpyAsync(L.a.x_old, L.a.x_adv, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+            k_apgd_sched(L.a.st.sched, L.a.st.ctr, N, s);
+            if ((rc = run_iterations(m, "vl_apgdt_attack", key, N + 1, s, [&](int, hipStream_t sc) { return apgdt_iteration(m, L, B, N, eps, rho, sc); })))
+                return rc;
+            if (a->loss_best) HIPCHK(hipMemcpyAsync(a->loss_best + (size_t)run * B, L.a.st.loss_best, row, hipMemcpyDeviceToDevice, s));
+            if (a->robust_run) HIPCHK(hipMemcpyAsync(a->robust_run + (size_t)run * B, L.a.st.robust, row, hipMemcpyDeviceToDevice, s));
+            k_apgdt_fold(L.x_out, L.a.x_best_adv, L.still[run & 1], L.still[(run + 1) & 1], L.a.st.robust, L.fooled_by, run, B, n_img, s);
+        }
+    }
+    if (a->x_adv) HIPCHK(hipMemcpyAsync(a->x_adv, L.x_out, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (a->robust) HIPCHK(hipMemcpyAsync(a->robust, L.still[run & 1], row, hipMemcpyDeviceToDevice, s));
+    if (a->clean_correct) HIPCHK(hipMemcpyAsync(a->clean_correct, L.clean_correct, row, hipMemcpyDeviceToDevice, s));
+    if (a->targets) HIPCHK(hipMemcpyAsync(a->targets, L.targets, (size_t)K * row, hipMemcpyDeviceToDevice, s));
+    if (a->fooled_by) HIPCHK(hipMemcpyAsync(a->fooled_by, L.fooled_by, row, hipMemcpyDeviceToDevice, s));
+    if (a->trace_loss) HIPCHK(hipMemcpyAsync(a->trace_loss, L.a.st.tr_loss, (size_t)(N + 1) * row, hipMemcpyDeviceToDevice, s));
+    if (a->trace_step) HIPCHK(hipMemcpyAsync(a->trace_step, L.a.st.tr_step, (size_t)N * row, hipMemcpyDeviceToDevice, s));
+    if (a->trace_pred) HIPCHK(hipMemcpyAsync(a->trace_pred, L.a.st.tr_pred, (size_t)(N + 1) * row, hipMemcpyDeviceToDevice, s));
+    return VL_OK;
+}
+
 #ifndef VL_BF16
+int vl_dlr_targeted_loss(const float* logits, const int64_t* labels, const int32_t* targets, int B, int C, float* loss_img,
+                         float* dlogits, int* err_flag, void* stream) {
+    if (!logits || !labels || !targets || !loss_img || !dlogits || B <= 0) return fail(VL_ERR_ARG, "bad argument");
+    if (C < 4) return fail(VL_ERR_UNSUPPORTED, "the DLR loss needs at least 4 classes");
+    k_dlr_targeted_loss(logits, labels, targets, B, C, dlogits, loss_img, nullptr, err_flag, (hipStream_t)stream);
+    return VL_OK;
+}
+
+int vl_apgd_targets(const float* logits, const int64_t* labels, int B, int C, int n_target, int32_t* targets,
+                    int32_t* clean_correct, void* stream) {
+    if (!logits || !labels || !targets || !clean_correct || B <= 0 || C < 2) return fail(VL_ERR_ARG, "bad argument");
+    if (n_target < 1 || n_target > C - 1) return fail(VL_ERR_ARG, "n_target must be 1 .. C - 1");
+    k_apgd_targets(logits, labels, B, C, n_target, targets, clean_correct, (hipStream_t)stream);
+    return VL_OK;
+}
+
 int vl_apgd_step(float* x_adv, float* x_old, float* x_best, float* x_best_adv, float* grad_best, const float* x0,
                  const float* grad, const uint32_t* flags, const float* step, int batch, int64_t image_elems, float eps,
                  float a, int last, void* stream) {

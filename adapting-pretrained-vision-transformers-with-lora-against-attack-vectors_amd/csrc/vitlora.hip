@@ -258,6 +258,7 @@ int check_async(vl_model* m) {
                                    "redo that batch with precision = f32 or bf16");
         if (code == 5) return fail(VL_ERR_NONFINITE, "an earlier vl_square_attack saw a margin that was not finite (the logits left the "
                                    "number range): that query was not accepted; redo the batch with precision = f32 or bf16");
+        if (code == 6) return fail(VL_ERR_ARG, "a target class of an earlier vl_apgdt_attack was outside [0, num_labels) or equal to the label");
         return fail(VL_ERR_HIP, "device-side error flag %d", code);
     }
     return VL_OK;

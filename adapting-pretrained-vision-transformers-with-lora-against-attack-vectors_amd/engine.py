@@ -375,6 +375,84 @@ class Engine:
         check(self.lib.vl_debug_apgd_track(self.h, C.byref(c), self._stream()), "vl_debug_apgd_track")
         return step, flags, best, robust
 
+    # -- APGD-T (targeted Auto-PGD on the DLR loss, L-inf) --------------------------------------------
+    def apgdt_scratch_bytes(self, batch: int, steps: int, n_target_classes: int) -> int:
+        n = C.c_size_t()
+        check(self.lib.vl_apgdt_scratch_bytes(self.h, int(batch), int(steps), int(n_target_classes), C.byref(n)),
+              "vl_apgdt_scratch_bytes")
+        return n.value
+
+    def apgdt_attack(self, x0: torch.Tensor, labels: torch.Tensor, eps, steps=100, rho=0.75, n_target_classes=9, n_restarts=1,
+                     seed=0, targets: Optional[torch.Tensor] = None, trace=False, scratch=None) -> Dict[str, torch.Tensor]:
+        """vl_apgdt_attack.  runs = n_target_classes * n_restarts, run = k * n_restarts + r uses the seed `seed + run`.  Returns
+        {"x_adv", "robust" [B] bool, "clean_correct" [B] bool, "targets" [n_target_classes, B] int32, "fooled_by" [B] int32 (the
+        first run that fooled the image, -1: none), "loss_best" [runs, B], "robust_run" [runs, B] bool} and with trace=True also
+        the LAST run's {"trace_loss" [steps+1, B], "trace_step" [steps, B], "trace_pred" [steps+1, B] bool}.
+        targets: [n_target_classes, B] classes to aim at instead of the ones picked from the clean logits.
+        scratch: (base pointer, bytes) of a caller-owned buffer instead of the cached one (tests)."""
+        x0 = self._check_images(x0)
+        labels = labels.to(device=self.device, dtype=torch.int64).contiguous()
+        B, steps, K, R = x0.shape[0], int(steps), int(n_target_classes), int(n_restarts)
+        self.plan(B, False)
+        if scratch is None:
+            _, base, nbytes = self._attack_scratch("apgdt", (B, steps, K), self.apgdt_scratch_bytes)
+        else:
+            base, nbytes = scratch
+        tin = None
+        if targets is not None:
+            tin = targets.to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(tin.shape) != (K, B):
+                raise ValueError(f"targets must be [{K}, {B}] (n_target_classes, batch), got {tuple(tin.shape)}")
+        runs = max(K, 0) * max(R, 0)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        out = {"x_adv": torch.empty_like(x0), "robust": torch.empty(B, **i32), "clean_correct": torch.empty(B, **i32),
+               "targets": torch.empty(max(K, 0), B, **i32), "fooled_by": torch.empty(B, **i32),
+               "loss_best": torch.empty(runs, B, dtype=torch.float32, device=self.device), "robust_run": torch.empty(runs, B, **i32)}
+        if trace:
+            out["trace_loss"] = torch.empty(steps + 1, B, dtype=torch.float32, device=self.device)
+            out["trace_step"] = torch.empty(steps, B, dtype=torch.float32, device=self.device)
+            out["trace_pred"] = torch.empty(steps + 1, B, **i32)
+        a = _lib.VLApgdtArgs()
+        a.x0, a.labels, a.batch, a.steps = x0.data_ptr(), labels.data_ptr(), B, steps
+        a.eps, a.rho, a.n_target_classes, a.n_restarts = float(eps), float(rho), K, R
+        a.seed = int(seed) & (2 ** 64 - 1)
+        a.targets_in = tin.data_ptr() if tin is not None else None
+        a.scratch, a.scratch_bytes = base, nbytes
+        for k, t in out.items():
+            setattr(a, k, t.data_ptr())
+        a.stream = self._stream().value
+        check(self.lib.vl_apgdt_attack(self.h, C.byref(a)), "vl_apgdt_attack")
+        self._keep, self._keep_labels, self._keep_init = x0, labels, tin
+        for k in ("robust", "clean_correct", "robust_run") + (("trace_pred",) if trace else ()):
+            out[k] = out[k] != 0
+        return out
+
+    def dlr_targeted_loss(self, logits: torch.Tensor, labels: torch.Tensor, targets: torch.Tensor):
+        """vl_dlr_targeted_loss on caller tensors: logits [B, C] fp32, labels [B], targets [B].  Returns (loss [B], D * dloss/dlogits
+        [B, C], err [1] int32: 0, 1 = a label out of range, 6 = a target out of range or equal to the label)."""
+        lg = self._f32(logits)
+        y = labels.to(device=self.device, dtype=torch.int64).contiguous()
+        t = targets.to(device=self.device, dtype=torch.int32).contiguous()
+        B, Cn = lg.shape
+        loss = torch.empty(B, dtype=torch.float32, device=self.device)
+        d = torch.empty(B, Cn, dtype=torch.float32, device=self.device)
+        err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        check(self.lib.vl_dlr_targeted_loss(C.c_void_p(lg.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(t.data_ptr()), B, Cn,
+                                            C.c_void_p(loss.data_ptr()), C.c_void_p(d.data_ptr()), C.c_void_p(err.data_ptr()),
+                                            self._stream()), "vl_dlr_targeted_loss")
+        return loss, d, err
+
+    def apgd_targets(self, logits: torch.Tensor, labels: torch.Tensor, n_target: int):
+        """vl_apgd_targets on caller tensors: (targets [n_target, B] int32, clean_correct [B] bool)."""
+        lg = self._f32(logits)
+        y = labels.to(device=self.device, dtype=torch.int64).contiguous()
+        B, Cn = lg.shape
+        t = torch.empty(int(n_target), B, dtype=torch.int32, device=self.device)
+        cc = torch.empty(B, dtype=torch.int32, device=self.device)
+        check(self.lib.vl_apgd_targets(C.c_void_p(lg.data_ptr()), C.c_void_p(y.data_ptr()), B, Cn, int(n_target),
+                                       C.c_void_p(t.data_ptr()), C.c_void_p(cc.data_ptr()), self._stream()), "vl_apgd_targets")
+        return t, cc != 0
+
     # -- Square attack (score-based random search, L-inf) ---------------------------------------------
     def square_scratch_bytes(self, batch: int, n_queries: int) -> int:
         n = C.c_size_t()

@@ -2,18 +2,21 @@
 """AutoAttack's "auto" split on MI355X -- command-line compatible with the reference's auto_attack.py (flags: auto_attack.py:12-21;
 directory layout <out>/<model>/<source>/<split>/auto/images/*.png + auto/metadata.csv: :60-68,112-115).
 
-The reference runs AutoAttack(norm='Linf', eps, version='standard', seed=42) on every batch (:98-108).  Of that suite the first
-component, APGD-CE (vl_apgd_attack: the whole Auto-PGD loop on the device), and the last, Square (vl_square_attack: score-based
-random search on the logits, no gradient), are built.  By default this script runs AutoAttack(version='custom',
-attacks_to_run=['apgd-ce']): an image that is classified correctly and that APGD-CE fools is replaced by the misclassified point,
-every other image is written as it was.  --attacks apgd-ce square adds Square for the images APGD-CE leaves robust -- the
-gradient-free cross-check of an adapter that may only be masking its gradients.  APGD-T and FAB-T are not built.
+The reference runs AutoAttack(norm='Linf', eps, version='standard', seed=42) on every batch (:98-108).  Of that suite
+(APGD-CE, APGD-T, FAB-T, Square) three components are built: APGD-CE (vl_apgd_attack: the whole Auto-PGD loop on the device),
+APGD-T (vl_apgdt_attack: targeted Auto-PGD on the DLR loss, every target class and the fold over them on the device) and Square
+(vl_square_attack: score-based random search on the logits, no gradient).  By default this script runs run_suite(attacks=
+['apgd-ce']): an image that is classified correctly and that APGD-CE fools is replaced by the misclassified point, every other
+image is written as it was.  --attacks apgd-ce apgd-t square runs each further component on the images the earlier ones leave
+robust: APGD-T because cross-entropy saturates on an adapter that masks its gradients and the DLR ratio does not, Square as the
+gradient-free cross-check.  FAB-T is not built.  All three are restatements of the package from memory: parity unpinned.
 Extensions, all opt-in:
   --synthetic N           no dataset / checkpoint on disk: N seeded random images per split and seeded random-init weights.
   --arch tiny|vit_b|vit_l architecture of the checkpoint (default vit_b = google/vit-base-patch16-224).
   --precision f16|bf16|f32
   --steps K               APGD iterations (the package's standard version uses 100).
-  --attacks A [A ...]     components to run in order, from apgd-ce and square (default: apgd-ce).
+  --attacks A [A ...]     components to run in order, from apgd-ce, apgd-t and square (default: apgd-ce).
+  --n_target_classes K    APGD-T's target classes per image (the package's standard version uses 9; at most num_classes - 1).
   --square_queries N      Square's query budget (the package's standard version uses 5000).
   --check_every K         Square looks at the robust flags every K queries and stops once every image is fooled (0 = never look).
 """
@@ -30,7 +33,7 @@ V = importlib.import_module("adapting-pretrained-vision-transformers-with-lora-a
 
 
 def build_parser():
-    p = argparse.ArgumentParser(description="Generate AutoAttack (APGD-CE, Square; MI355X / HIP)")
+    p = argparse.ArgumentParser(description="Generate AutoAttack (APGD-CE, APGD-T, Square; MI355X / HIP)")
     p.add_argument("--data_root", required=False, default=None)
     p.add_argument("--model", required=True, help="Model architecture name of the output tree (e.g., google_vit)")
     p.add_argument("--source", required=True, help="Source dataset (e.g., gtsrb)")
@@ -45,7 +48,8 @@ def build_parser():
     p.add_argument("--precision", choices=["f16", "bf16", "f32"], default="f16")
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--seed", type=int, default=42)
-    p.add_argument("--attacks", nargs="+", choices=["apgd-ce", "square"], default=["apgd-ce"])
+    p.add_argument("--attacks", nargs="+", choices=["apgd-ce", "apgd-t", "square"], default=["apgd-ce"])
+    p.add_argument("--n_target_classes", type=int, default=9)
     p.add_argument("--square_queries", type=int, default=5000)
     p.add_argument("--check_every", type=int, default=0)
     return p
@@ -97,6 +101,7 @@ def main(argv=None):
     model, class_to_idx = load_model(args, device)
     mean, std = V.get_normalization(args.model)
     engine = model._engine()
+    n_target = max(1, min(args.n_target_classes, len(class_to_idx) - 1))
     for split in args.splits:
         print(f"\nProcessing {split} split...")
         output_dir = os.path.join(args.output_dir, args.model, args.source, split, "auto", "images")
@@ -106,17 +111,18 @@ def main(argv=None):
             images, labels = images.to(device), labels.to(device)
             offset = len(seen)                # Square draws by the image's index in the split, not by its place in the batch
             seen.extend(filenames)
-            adversary = V.AutoAttack(model, norm="Linf", eps=args.epsilon, version="custom", attacks_to_run=args.attacks,
-                                     seed=args.seed, steps=args.steps, mean=mean, std=std, square_queries=args.square_queries,
-                                     check_every=args.check_every)
-            x_adv = adversary.run_standard_evaluation(images, labels, bs=args.batch_size, image_offset=offset)
+            x_adv, robust_accuracy = V.run_suite(model, images, labels, args.epsilon, attacks=args.attacks, bs=args.batch_size,
+                                                 seed=args.seed, steps=args.steps, n_target_classes=n_target,
+                                                 square_queries=args.square_queries, check_every=args.check_every, mean=mean,
+                                                 std=std, image_offset=offset)
             engine.check()                   # synchronises; fp16 mode: raises if a gradient left the fp16 range
-            n_robust += round(adversary.robust_accuracy * len(filenames))
+            n_robust += round(robust_accuracy * len(filenames))
             iomod.save_images(x_adv, filenames, output_dir, engine=engine)
         if args.attacks == ["apgd-ce"]:
             print(f"  robust accuracy under APGD-CE (eps {args.epsilon:g}, {args.steps} steps): {n_robust}/{len(seen)}")
         else:
-            budget = {"apgd-ce": f"{args.steps} steps", "square": f"{args.square_queries} queries"}
+            budget = {"apgd-ce": f"{args.steps} steps", "apgd-t": f"{n_target} targets × {args.steps} steps",
+                      "square": f"{args.square_queries} queries"}
             print(f"  robust accuracy under {' + '.join(args.attacks)} (eps {args.epsilon:g}, "
                   f"{', '.join(budget[a] for a in args.attacks)}): {n_robust}/{len(seen)}")
         if not args.synthetic:

@@ -254,6 +254,73 @@ typedef struct vl_apgd_track_case {
 } vl_apgd_track_case;
 int vl_debug_apgd_track(vl_model* m, const vl_apgd_track_case* c, void* stream);
 
+/* ---- Targeted Auto-PGD on the DLR loss, L-inf (APGD-T): the second component of AutoAttack(model, norm='Linf', eps,
+ * version='standard').  The algorithm is the restatement in DESIGN.md section 3.11 and tests/apgdt_ref.py, written from memory of
+ * the autoattack package's autopgd_base.py (APGDAttack_targeted; not installed here): PARITY WITH THE PACKAGE IS UNPINNED.
+ *   1. one eval-mode forward of x0: clean_correct[b] = (argmax == labels[b]);
+ *   2. target k = 0 .. n_target_classes - 1 of image b = the class with the (k + 1)-th largest clean logit among the classes
+ *      != labels[b], ties broken by the lower class index (or row k of targets_in).  DEVIATION: the package takes
+ *      sort(logits)[:, -(k + 2)], which is the same class for every clean-correct image -- the only images whose result is used;
+ *   3. for each target k, for each restart r: one APGD run of `steps` iterations -- the schedule, step rule, momentum,
+ *      checkpoints and rho of vl_apgd_attack, started as its random_start = 1 does with the seed `seed + k * n_restarts + r` --
+ *      that MAXIMISES the DLR-targeted loss  -(z_y - z_t) / (z_pi1 - (z_pi3 + z_pi4) / 2 + 1e-12), pi = the descending order of
+ *      the logits row (value descending, index ascending); num_labels >= 4;
+ *   4. an image counts as fooled when argmax != label, as in the package: hitting the target is not required;
+ *   5. after each run, an image that was still robust and that the run fooled takes the run's x_best_adv; robust &= the run's.
+ *      Clean-wrong images and images no run fooled keep x0 bit for bit.
+ * What is back-propagated is D * dloss/dlogits, D = the loss's denominator > 0 (only the sign of the input gradient is used and
+ * the backward rescales each image anyway; dloss/dlogits itself carries 1 / D^2).
+ * One iteration (forward, DLR loss, backward to the input, apgd_track_kernel, apgd_step_kernel) is captured once per (batch, steps,
+ * eps, rho, scratch) and replayed runs * (steps + 1) times, runs = n_target_classes * n_restarts: the loss kernel reads the
+ * current target row from a fixed place in the scratch, refreshed between runs.  No device-to-host copy, no stream synchronisation.
+ * ALL state lives in `scratch` (vl_apgdt_scratch_bytes; 256-byte aligned): the APGD state, the target table, x_adv and the fold's
+ * flags.  The per-run rows (loss_best, robust_run) go straight to the caller's buffers after each run, so the scratch does not grow
+ * with n_restarts.  vl_plan and the workspace are unchanged.
+ * Refused (nothing is launched): num_labels < 4 (VL_ERR_UNSUPPORTED); n_target_classes outside 1 .. num_labels - 1,
+ * n_restarts < 1, eps not finite or < 0, rho outside [0, 1], batch, steps and scratch as vl_apgd_attack.  A label outside
+ * [0, num_labels), or a target in targets_in that is outside it or equals the label, gives that image NaN losses and makes a
+ * LATER call return an error. */
+typedef struct vl_apgdt_args {
+    const float* x0;          /* [B,3,S,S] fp32 in [0,1] */
+    const int64_t* labels;    /* [B] */
+    int32_t batch;
+    int32_t steps;            /* n_iter >= 1 */
+    float eps;
+    float rho;                /* .75 */
+    int32_t n_target_classes; /* 1 .. num_labels - 1 (the package: 9) */
+    int32_t n_restarts;       /* >= 1 */
+    uint64_t seed;
+    const int32_t* targets_in;/* NULL = pick from the clean logits, or [n_target_classes][B] */
+    void* scratch;
+    size_t scratch_bytes;
+    /* outputs, each may be NULL; runs = n_target_classes * n_restarts, run = k * n_restarts + r */
+    float* x_adv;             /* [B,3,S,S] */
+    int32_t* robust;          /* [B] clean_correct and robust in every run */
+    int32_t* clean_correct;   /* [B] */
+    int32_t* targets;         /* [n_target_classes][B] */
+    int32_t* fooled_by;       /* [B] the first run that fooled the image (and gave x_adv), -1 if none or clean-wrong */
+    float* loss_best;         /* [runs][B] */
+    int32_t* robust_run;      /* [runs][B] */
+    /* optional trace of the LAST run, shapes as vl_apgd_args */
+    float* trace_loss;
+    float* trace_step;
+    int32_t* trace_pred;
+    void* stream;
+    int32_t reserved[4];
+} vl_apgdt_args;
+int vl_apgdt_scratch_bytes(vl_model* m, int batch, int steps, int n_target_classes, size_t* bytes);
+int vl_apgdt_attack(vl_model* m, const vl_apgdt_args* args);
+
+/* One launch of dlr_targeted_loss_kernel on CALLER-OWNED buffers (tests): logits [B][C] fp32, labels [B] int64, targets [B] int32,
+ * C >= 4; loss_img [B] and dlogits [B][C] (= D * dloss/dlogits, see above) are written.  err_flag: NULL, or one device-visible int
+ * that is set to 1 for a label outside [0, C) and to 6 for a target outside it or equal to the label (that row: NaN). */
+int vl_dlr_targeted_loss(const float* logits, const int64_t* labels, const int32_t* targets, int B, int C, float* loss_img,
+                         float* dlogits, int* err_flag, void* stream);
+/* One launch of apgd_targets_kernel on CALLER-OWNED buffers (tests): targets [n_target][B] int32, clean_correct [B] int32;
+ * 1 <= n_target <= C - 1. */
+int vl_apgd_targets(const float* logits, const int64_t* labels, int B, int C, int n_target, int32_t* targets,
+                    int32_t* clean_correct, void* stream);
+
 /* ---- Square attack, L-inf (Andriushchenko et al. 2020): the LAST component of AutoAttack(model, norm='Linf', eps,
  * version='standard'), which auto_attack.py:98-108 runs -- a score-based random search that reads only the logits, the suite's
  * gradient-free cross-check.  The algorithm is the restatement in DESIGN.md section 3.10 and tests/square_ref.py, written from
