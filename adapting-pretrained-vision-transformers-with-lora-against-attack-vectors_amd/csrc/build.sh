@@ -1,14 +1,16 @@
 #!/bin/bash
 # Build libvitlora_hip.so for gfx950 (cross-compiles without a GPU).
-# The 16-bit operand path is compiled TWICE from the same sources: fp16 operands (namespace vl_f16, also carries the fp32 parity
-# mode, Swin-T and the handle-less entry points) and -DVL_BF16 (namespace vl_bf16); api_dispatch.cpp (generated) exports the ABI.
+# The 16-bit operand path is compiled TWICE from the same sources: fp16 operands (namespace vl_f16) and -DVL_BF16 (namespace
+# vl_bf16); api_dispatch.cpp (generated) exports the ABI.  Compiled ONCE: the kernels that never touch a 16-bit operand
+# (once_kernels.hip, namespace vl_once), process-wide state and the entry points without a handle (process_wide.hip, patch.hip),
+# and, in the fp16 build's namespace, the fp32 parity mode and Swin-T.
 set -e
 cd "$(dirname "$0")"
 OUT=../libvitlora_hip.so
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result"
 mkdir -p build
 python3 gen_dispatch.py > /dev/null
-HDRS="common.h kernels.h gemm.h prof.h model.h f32_kernels.h gemm_epi.h api_rename.h env.h ../../include/vitlora.h"
+HDRS="common.h kernels.h once_kernels.h gemm.h prof.h model.h f32_kernels.h gemm_epi.h api_rename.h env.h ../../include/vitlora.h"
 stale() {   # stale <object> <source>
   [ ! -f "$1" ] && return 0
   [ "$2" -nt "$1" ] && return 0
@@ -16,7 +18,7 @@ stale() {   # stale <object> <source>
   return 1
 }
 BOTH="gemm gemm256 gemm_pp gemm_stream elementwise attention32 cls_path lora_grad vitlora vit_attacks"
-ONCE="f32_kernels patch swin vitlora_f32"
+ONCE="once_kernels process_wide f32_kernels patch swin vitlora_f32"
 pids=()
 njobs=0
 run() { "$@" & pids+=($!); njobs=$((njobs + 1)); if [ $njobs -ge 8 ]; then wait -n || exit 1; njobs=$((njobs - 1)); fi; }

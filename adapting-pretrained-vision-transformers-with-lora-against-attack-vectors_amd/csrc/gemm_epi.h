@@ -8,7 +8,7 @@
 // and NOT kept: inside the PGD iteration these operands are served from the Infinity Cache (adv / x0 stay resident between
 // iterations, gelu'(z) and the stream rows were written a few kernels earlier) and the non-temporal form loses those hits
 // (patch-gradient + PGD-step GEMM 0.19 -> 0.26 ms, GELU-backward GEMM +2 %, 527 -> 521 img/s).  The standalone K10, whose
-// 617 MB do not fit the cache, gains 20 % from the same loads (elementwise.hip).
+// 617 MB do not fit the cache, gains 20 % from the same loads (once_kernels.hip).
 #ifndef VL_EPI_NT
 #define VL_EPI_NT 0
 #endif

@@ -125,8 +125,11 @@ struct PgdFuse { float* adv; const float* x0; float eps, alpha; };
 
 }  // namespace VLNS
 
-// what the handle-less entry points (vl_adam_step: fp16 build only) need to know about a live handle of EITHER build
+// what the handle-less entry points (vl_adam_step: process_wide.hip) need to know about a live handle of EITHER build
 struct VlFlatRecord { void* model; float* flat; int64_t flat_n; int* dirty; int** err_flag; };
+// process-wide state, defined once in process_wide.hip (the profiler and the LDS-poison switch: prof.h)
+extern std::vector<VlFlatRecord> g_vl_models;      // live handles of BOTH builds (vl_adam_step finds the model a flat buffer belongs to)
+extern long long g_poison_count;
 
 struct vl_model {
     vl_config cfg;
@@ -182,14 +185,15 @@ struct vl_model {
 
 static_assert(offsetof(vl_model, cfg) == 0, "api_dispatch.cpp reads the precision through the vl_config the handle starts with");
 
-// helpers defined in vitlora.hip
-int vl_fail(int code, const char* fmt, ...);
+int vl_fail(int code, const char* fmt, ...);      // process_wide.hip: records the text vl_last_error returns, returns `code`
 #define HIPCHK(expr)                                                                            \
     do {                                                                                        \
         hipError_t e_ = (expr);                                                                 \
         if (e_ != hipSuccess) return vl_fail(VL_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+// helpers defined in vitlora.hip
 namespace VLNS {
+bool capturing(hipStream_t s);            // the stream is inside a stream capture (launch errors are then read after the replay)
 bool vl_drop_on(const vl_model* m, const Pass& p);      // LoRA dropout applies to the forward that pass `p` holds
 int check_async(vl_model* m);             // errors a kernel reported through the pinned host word, surfaced by the next API call
 int check_launch(const char* what);       // sticky launch failures, read after a launch sequence that ran OUTSIDE stream capture

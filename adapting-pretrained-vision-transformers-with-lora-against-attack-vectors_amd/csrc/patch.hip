@@ -14,10 +14,12 @@
 // installable here, so the oracle (oracle/patch_oracle.py) is a torch restatement of the same formulas and these
 // kernels are held to it ("parity unpinned").  The host passes the INVERSE affine matrix per image (6 floats,
 // torchvision's _get_inverse_affine_matrix, computed in double); both kernels are HBM-bound elementwise passes.
-#include "kernels.h"
+#include "model.h"
 #include "prof.h"
 
-namespace VLNS {      // vl_f16 / vl_bf16: the 16-bit path is compiled once per operand type (common.h)
+#define fail vl_fail
+
+namespace VLNS {      // compiled once (build.sh), in the fp16 build's namespace: check_launch / capturing are vitlora.hip's
 
 namespace {
 
@@ -163,7 +165,7 @@ __global__ __launch_bounds__(256) void patch_overlay_kernel(const float* __restr
 //      not depend on the order in which lanes and workgroups arrive.  The workgroup that arrives last converts the scratch image
 //      to fp32, writes the result and leaves the scratch zeroed for the next call.
 // A non-finite pixel gradient turns the whole result into NaN (the backward's non-finite flag has fired upstream in that case).
-constexpr int PS_MAX = 64;                               // patch_args_ok (vitlora.hip)
+constexpr int PS_MAX = 64;                               // patch_args_ok below
 __device__ unsigned long long g_patch_acc[3 * PS_MAX * PS_MAX];     // zero between calls; calls on one device are stream-ordered by the caller
 __device__ unsigned g_patch_arrived, g_patch_poison, g_patch_max_bits;
 
@@ -311,5 +313,47 @@ void k_clamp(float* x, float lo, float hi, int64_t n, hipStream_t s) {
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(clamp_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(256), 0, s, x, lo, hi, n);
 }
+
+// ---- entry points (patch_attack.py: ART AdversarialPatchPyTorch); no handle: they exist once, like this file ----
+extern "C" {
+
+static int patch_args_ok(int batch, int image_size, int patch_size, int patch_type) {
+    if (batch <= 0 || image_size <= 0 || patch_size <= 0 || patch_size > 64 || patch_size > image_size)
+        return fail(VL_ERR_UNSUPPORTED, "patch_size must be in [1, min(64, image_size)]");
+    if (patch_type != 0 && patch_type != 1) return fail(VL_ERR_ARG, "patch_type: 0 = square, 1 = circle");
+    return VL_OK;
+}
+int vl_patch_apply_persp(const float* images, const float* patch, const float* inv_affine, const float* persp, int batch,
+                         int image_size, int patch_size, int patch_type, float* out, void* stream) {
+    if (!images || !patch || !inv_affine || !out || out == images) return fail(VL_ERR_ARG, "bad argument");
+    if (int rc = patch_args_ok(batch, image_size, patch_size, patch_type)) return rc;
+    k_patch_overlay(images, patch, inv_affine, persp, out, batch, image_size, patch_size, patch_type, (hipStream_t)stream);
+    if (!capturing((hipStream_t)stream)) return check_launch("vl_patch_apply");
+    return VL_OK;
+}
+int vl_patch_apply(const float* images, const float* patch, const float* inv_affine, int batch, int image_size, int patch_size,
+                   int patch_type, float* out, void* stream) {
+    return vl_patch_apply_persp(images, patch, inv_affine, nullptr, batch, image_size, patch_size, patch_type, out, stream);
+}
+int vl_patch_grad_persp(const float* grad_out, const float* inv_affine, const float* persp, int batch, int image_size,
+                        int patch_size, int patch_type, float* patch_grad, void* stream) {
+    if (!grad_out || !inv_affine || !patch_grad) return fail(VL_ERR_ARG, "bad argument");
+    if (int rc = patch_args_ok(batch, image_size, patch_size, patch_type)) return rc;
+    k_patch_overlay_bwd(grad_out, inv_affine, persp, patch_grad, batch, image_size, patch_size, patch_type, (hipStream_t)stream);
+    if (!capturing((hipStream_t)stream)) return check_launch("vl_patch_grad");
+    return VL_OK;
+}
+int vl_patch_grad(const float* grad_out, const float* inv_affine, int batch, int image_size, int patch_size, int patch_type,
+                  float* patch_grad, void* stream) {
+    return vl_patch_grad_persp(grad_out, inv_affine, nullptr, batch, image_size, patch_size, patch_type, patch_grad, stream);
+}
+
+int vl_clamp(float* x, float lo, float hi, int64_t n, void* stream) {
+    if (!x || n <= 0 || !(lo <= hi)) return fail(VL_ERR_ARG, "bad argument");
+    k_clamp(x, lo, hi, n, (hipStream_t)stream);
+    return VL_OK;
+}
+
+}  // extern "C"
 
 }  // namespace VLNS

@@ -17,7 +17,7 @@ struct Profiler {
     std::vector<ProfRecord> recs;
 };
 
-extern Profiler* g_prof;   // defined in vitlora.hip; non-null only between begin and report
+extern Profiler* g_prof;   // defined in process_wide.hip; non-null only between begin and report
 
 // Test hook (vl_debug_set_option "poison_lds"): when non-zero, every launch that has a ProfScope is preceded by a kernel that
 // fills the whole LDS of every CU with NaN patterns -- a kernel that reads LDS it did not write then shows as a changed result

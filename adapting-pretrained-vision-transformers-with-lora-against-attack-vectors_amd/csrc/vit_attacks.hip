@@ -14,7 +14,6 @@
 #include "model.h"
 #include "prof.h"
 
-// This file is compiled twice (common.h): the entry points without a handle exist once, in the fp16 build.
 #define fail vl_fail
 
 namespace VLNS {
@@ -200,12 +199,14 @@ size_t apgd_carve(const vl_model* m, int B, int N, char* base, ApgdLayout& L) {
 size_t apgd_bytes(const vl_model* m, int batch, int steps) { ApgdLayout sz; return apgd_carve(m, batch, steps, nullptr, sz); }
 const ScratchSpec kApgdScratch = {"APGD", "steps", "vl_apgd_scratch_bytes", apgd_bytes};
 
-// one APGD iteration in the main pass: evaluate x_adv (forward, CE, gradient to grad_img), then bookkeeping and the next point
-int apgd_iteration(vl_model* m, const ApgdLayout& L, int B, int N, float eps, float rho, hipStream_t s) {
+// one APGD / APGD-T iteration in the main pass: evaluate x_adv (forward, the loss that loss(p, s) launches -- CE or DLR-targeted --,
+// gradient to grad_img), then bookkeeping and the next point
+template <typename LossFn>
+int apgd_iteration(vl_model* m, const ApgdLayout& L, int B, int N, float eps, float rho, hipStream_t s, LossFn loss) {
     Pass& p = m->main;
     int rc = forward_impl(m, p, L.x_adv, B, 1, 0, s);
     if (rc) return rc;
-    k_ce_loss(p.ws.logits, L.labels, B, m->C, p.ws.dlogits, p.ws.loss_img, p.ws.loss, m->err_flag, s);
+    loss(p, s);
     p.have_loss = 1;
     if ((rc = backward_impl(m, p, p.ws.grad_img, nullptr, s))) return rc;
     k_apgd_track(L.st, p.ws.loss_img, p.ws.logits, L.labels, B, m->C, N, eps, rho, s);
@@ -235,20 +236,6 @@ size_t apgdt_carve(const vl_model* m, int B, int N, int n_target, char* base, Ap
 // the shared scratch check sizes APGD's part (batch, steps); the whole size is checked by the caller, which knows n_target
 size_t apgdt_bytes_min(const vl_model* m, int batch, int steps) { ApgdtLayout sz; return apgdt_carve(m, batch, steps, 1, nullptr, sz); }
 const ScratchSpec kApgdtScratch = {"APGD-T", "steps", "vl_apgdt_scratch_bytes", apgdt_bytes_min};
-
-// one APGD-T iteration in the main pass: APGD's with the DLR-targeted loss towards target_cur
-int apgdt_iteration(vl_model* m, const ApgdtLayout& L, int B, int N, float eps, float rho, hipStream_t s) {
-    Pass& p = m->main;
-    int rc = forward_impl(m, p, L.a.x_adv, B, 1, 0, s);
-    if (rc) return rc;
-    k_dlr_targeted_loss(p.ws.logits, L.a.labels, L.target_cur, B, m->C, p.ws.dlogits, p.ws.loss_img, p.ws.loss, m->err_flag, s);
-    p.have_loss = 1;
-    if ((rc = backward_impl(m, p, p.ws.grad_img, nullptr, s))) return rc;
-    k_apgd_track(L.a.st, p.ws.loss_img, p.ws.logits, L.a.labels, B, m->C, N, eps, rho, s);
-    k_apgd_step(L.a.x_adv, L.a.x_old, L.a.x_best, L.a.x_best_adv, L.a.grad_best, L.a.x0, p.ws.grad_img, L.a.st.flags, L.a.st.step, B,
-                (int64_t)3 * m->S * m->S, eps, L.a.st.sched, L.a.st.ctr, N, 0.f, 0, s, m->err_flag);
-    return VL_OK;
-}
 
 // ---- Square attack (L-inf, margin loss; include/vitlora.h) -------------
 // Everything the attack keeps between replays, carved from the caller's scratch (base == nullptr: size only).
@@ -299,20 +286,6 @@ void drop_graphs(vl_model* m) {
 }
 
 extern "C" {
-
-#ifndef VL_BF16
-int vl_pgd_step(float* adv, const float* x0, const float* grad, float eps, float alpha, float lo, float hi, int64_t n, void* stream) {
-    if (!adv || !x0 || !grad || n <= 0) return fail(VL_ERR_ARG, "bad argument");
-    k_pgd_step(adv, x0, grad, eps, alpha, lo, hi, n, (hipStream_t)stream);
-    return VL_OK;
-}
-
-int vl_pgd_init(float* adv, const float* x0, float eps, float lo, float hi, uint64_t seed, int64_t n, void* stream) {
-    if (!adv || !x0 || n <= 0) return fail(VL_ERR_ARG, "bad argument");
-    k_pgd_init(adv, x0, eps, lo, hi, seed, n, (hipStream_t)stream);
-    return VL_OK;
-}
-#endif
 
 int vl_pgd_attack(vl_model* m, const float* x0, const int64_t* labels, int batch, float eps, float alpha, int steps,
                   int random_start, uint64_t seed, float* adv_out, void* stream) {
@@ -384,7 +357,10 @@ int vl_apgd_attack(vl_model* m, const vl_apgd_args* a) {
     k_apgd_sched(L.st.sched, L.st.ctr, N, s);
     m->fwd_chains = 0;
     const GraphKey key = {GRAPH_APGD, B, 1, N, eps, 0.f, rho, a->scratch};
-    if ((rc = run_iterations(m, "vl_apgd_attack", key, N + 1, s, [&](int, hipStream_t sc) { return apgd_iteration(m, L, B, N, eps, rho, sc); })))
+    auto ce_loss = [&](Pass& p, hipStream_t sc) {
+        k_ce_loss(p.ws.logits, L.labels, B, m->C, p.ws.dlogits, p.ws.loss_img, p.ws.loss, m->err_flag, sc);
+    };
+    if ((rc = run_iterations(m, "vl_apgd_attack", key, N + 1, s, [&](int, hipStream_t sc) { return apgd_iteration(m, L, B, N, eps, rho, sc, ce_loss); })))
         return rc;
     const size_t row = (size_t)B * 4;
     if (a->x_best) HIPCHK(hipMemcpyAsync(a->x_best, L.x_best, n * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -453,6 +429,9 @@ int vl_apgdt_attack(vl_model* m, const vl_apgdt_args* a) {
     HIPCHK(hipMemcpyAsync(L.still[0], L.clean_correct, row, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemsetAsync(L.fooled_by, 0xFF, row, s));                  // -1
     const GraphKey key = {GRAPH_APGDT, B, 1, N, eps, 0.f, rho, a->scratch};
+    auto dlr_loss = [&](Pass& p, hipStream_t sc) {      // APGD's iteration with the DLR-targeted loss towards target_cur
+        k_dlr_targeted_loss(p.ws.logits, L.a.labels, L.target_cur, B, m->C, p.ws.dlogits, p.ws.loss_img, p.ws.loss, m->err_flag, sc);
+    };
     int run = 0;
     for (int k = 0; k < K; ++k) {
         HIPCHK(hipMemcpyAsync(L.target_cur, L.targets + (size_t)k * B, row, hipMemcpyDeviceToDevice, s));
@@ -460,7 +439,7 @@ int vl_apgdt_attack(vl_model* m, const vl_apgdt_args* a) {
             k_apgd_rand_init(L.a.x_adv, L.a.x0, eps, a->seed + (uint64_t)run, B, n_img, s);
             HIPCHK(hipMemcpyAsync(L.a.x_old, L.a.x_adv, n * sizeof(float), hipMemcpyDeviceToDevice, s));
             k_apgd_sched(L.a.st.sched, L.a.st.ctr, N, s);
-            if ((rc = run_iterations(m, "vl_apgdt_attack", key, N + 1, s, [&](int, hipStream_t sc) { return apgdt_iteration(m, L, B, N, eps, rho, sc); })))
+            if ((rc = run_iterations(m, "vl_apgdt_attack", key, N + 1, s, [&](int, hipStream_t sc) { return apgd_iteration(m, L.a, B, N, eps, rho, sc, dlr_loss); })))
                 return rc;
             if (a->loss_best) HIPCHK(hipMemcpyAsync(a->loss_best + (size_t)run * B, L.a.st.loss_best, row, hipMemcpyDeviceToDevice, s));
             if (a->robust_run) HIPCHK(hipMemcpyAsync(a->robust_run + (size_t)run * B, L.a.st.robust, row, hipMemcpyDeviceToDevice, s));
@@ -477,38 +456,6 @@ int vl_apgdt_attack(vl_model* m, const vl_apgdt_args* a) {
     if (a->trace_pred) HIPCHK(hipMemcpyAsync(a->trace_pred, L.a.st.tr_pred, (size_t)(N + 1) * row, hipMemcpyDeviceToDevice, s));
     return VL_OK;
 }
-
-#ifndef VL_BF16
-int vl_dlr_targeted_loss(const float* logits, const int64_t* labels, const int32_t* targets, int B, int C, float* loss_img,
-                         float* dlogits, int* err_flag, void* stream) {
-    if (!logits || !labels || !targets || !loss_img || !dlogits || B <= 0) return fail(VL_ERR_ARG, "bad argument");
-    if (C < 4) return fail(VL_ERR_UNSUPPORTED, "the DLR loss needs at least 4 classes");
-    k_dlr_targeted_loss(logits, labels, targets, B, C, dlogits, loss_img, nullptr, err_flag, (hipStream_t)stream);
-    return VL_OK;
-}
-
-int vl_apgd_targets(const float* logits, const int64_t* labels, int B, int C, int n_target, int32_t* targets,
-                    int32_t* clean_correct, void* stream) {
-    if (!logits || !labels || !targets || !clean_correct || B <= 0 || C < 2) return fail(VL_ERR_ARG, "bad argument");
-    if (n_target < 1 || n_target > C - 1) return fail(VL_ERR_ARG, "n_target must be 1 .. C - 1");
-    k_apgd_targets(logits, labels, B, C, n_target, targets, clean_correct, (hipStream_t)stream);
-    return VL_OK;
-}
-
-int vl_apgd_step(float* x_adv, float* x_old, float* x_best, float* x_best_adv, float* grad_best, const float* x0,
-                 const float* grad, const uint32_t* flags, const float* step, int batch, int64_t image_elems, float eps,
-                 float a, int last, void* stream) {
-    if (!x_adv || !x_old || !x_best || !x_best_adv || !grad_best || !x0 || !grad || !flags || !step || batch <= 0 || batch > 65535 ||
-        image_elems <= 0 || image_elems % 4)
-        return fail(VL_ERR_ARG, "bad argument (image_elems must be a positive multiple of 4, batch 1 .. 65535)");
-    const void* ptrs[] = {x_adv, x_old, x_best, x_best_adv, grad_best, x0, grad};
-    for (const void* p : ptrs)
-        if ((uintptr_t)p & 15) return fail(VL_ERR_ARG, "image pointers must be 16-byte aligned");
-    k_apgd_step(x_adv, x_old, x_best, x_best_adv, grad_best, x0, grad, flags, step, batch, image_elems, eps, nullptr, nullptr, 0, a,
-                last ? 1 : 0, (hipStream_t)stream);
-    return VL_OK;
-}
-#endif
 
 int vl_square_scratch_bytes(vl_model* m, int batch, int n_queries, size_t* bytes) {
     if (!m || !bytes || batch <= 0 || n_queries < 1 || n_queries > 65535) return fail(VL_ERR_ARG, "bad argument");
@@ -580,18 +527,6 @@ int vl_debug_square_track(vl_model* m, const vl_square_track_case* c, void* stre
     if (c->queries_out) HIPCHK(hipMemcpyAsync(c->queries_out, L.st.queries, row, hipMemcpyDeviceToDevice, s));
     return VL_OK;
 }
-
-#ifndef VL_BF16
-int vl_square_step(float* x_cur, float* x_best, const float* x0, const uint32_t* flags, const int32_t* win_prev,
-                   const int32_t* win_next, int batch, int image_size, float eps, void* stream) {
-    if (!x_cur || !x_best || !x0 || !flags || !win_prev || !win_next || batch <= 0 || batch > 65535 || image_size <= 0 ||
-        image_size > 8192)
-        return fail(VL_ERR_ARG, "bad argument (batch 1 .. 65535, image_size 1 .. 8192)");
-    if (!(eps >= 0.f) || !(eps < INFINITY)) return fail(VL_ERR_ARG, "eps must be finite and >= 0");
-    k_square_step(x_cur, x_best, x0, flags, win_prev, win_next, batch, image_size, eps, nullptr, 0, (hipStream_t)stream);
-    return VL_OK;
-}
-#endif
 
 }  // extern "C"
 

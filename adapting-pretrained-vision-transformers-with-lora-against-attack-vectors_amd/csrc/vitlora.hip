@@ -1,10 +1,10 @@
 // C ABI of libvitlora_hip.so (include/vitlora.h): model handle, packed weights, workspace
 // plan and the launch sequences for forward, backward-to-input and LoRA backward, plus the
-// debug and profiling entry points.  The attacks (PGD, APGD, Square) and their graph cache
-// are in vit_attacks.hip.  Host-side orchestration only: all arithmetic is in
-// gemm*.hip / attention32.hip / cls_path.hip / elementwise.hip / lora_grad.hip.
+// debug entry points.  The attacks (PGD, APGD, Square) and their graph cache are in
+// vit_attacks.hip; process-wide state, profiling and the entry points without a handle in
+// process_wide.hip (patch.hip for the adversarial patch).  Host-side orchestration only: all arithmetic is in
+// gemm*.hip / attention32.hip / cls_path.hip / elementwise.hip / once_kernels.hip / lora_grad.hip.
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -17,47 +17,6 @@
 #include "model.h"
 #include "prof.h"
 
-// This file is compiled twice (common.h): process-wide state and the entry points without a handle exist once, in the fp16 build.
-extern std::vector<VlFlatRecord> g_vl_models;      // live handles of BOTH builds (vl_adam_step finds the model a flat buffer belongs to)
-extern long long g_poison_count;
-#ifndef VL_BF16
-Profiler* g_prof = nullptr;
-int g_poison_lds = 0;
-long long g_poison_count = 0;
-namespace {
-__global__ __launch_bounds__(256) void poison_lds_kernel(unsigned pattern, unsigned* sink) {
-    extern __shared__ unsigned lds_all[];
-    constexpr int N = 160 * 1024 / 4;
-    for (int i = threadIdx.x; i < N; i += 256) lds_all[i] = pattern;
-    __syncthreads();
-    if (sink && lds_all[(threadIdx.x * 97) % N] != pattern) *sink = 1;      // keeps the stores alive
-}
-}  // namespace
-void vl_poison_lds(hipStream_t s) {
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)poison_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
-    int dev = 0, cus = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    // one workgroup owns a CU's whole LDS, so 2 x #CUs workgroups reach every CU of an otherwise idle stream
-    hipLaunchKernelGGL(poison_lds_kernel, dim3(2 * cus), dim3(256), 160 * 1024, s, 0xFFFFFFFFu, (unsigned*)nullptr);
-    if (hipGetLastError() == hipSuccess) ++g_poison_count;
-}
-std::vector<VlFlatRecord> g_vl_models;
-namespace {
-thread_local std::string g_err;
-}
-
-int vl_fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-#endif
 #define fail vl_fail
 #define g_models g_vl_models
 
@@ -228,12 +187,6 @@ int parse_layer(const char* name, const char** rest) {
     return (int)i;
 }
 
-bool capturing(hipStream_t s) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return st != hipStreamCaptureStatusNone;
-}
-
 // the two switches read here that are neither a flag nor an integer (every other one goes through env.h)
 // VITLORA_RESID: "ln" = 0, "o" = 1, anything else or unset = 2 (vl_model::resid_epi)
 int env_resid() { const char* e = getenv("VITLORA_RESID"); return !e ? 2 : !strcmp(e, "ln") ? 0 : !strcmp(e, "o") ? 1 : 2; }
@@ -241,6 +194,12 @@ int env_resid() { const char* e = getenv("VITLORA_RESID"); return !e ? 2 : !strc
 int env_attn_img() { const char* e = getenv("VITLORA_ATTN_IMG"); return e ? (e[0] == '1' ? 1 : 0) : -1; }
 
 }  // namespace
+
+bool capturing(hipStream_t s) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return st != hipStreamCaptureStatusNone;
+}
 
 bool vl_drop_on(const vl_model* m, const Pass& p) { return p.train && m->r && m->cfg.lora_dropout > 0.f; }
 
@@ -280,13 +239,6 @@ int chain_resources(vl_model* m) {
 }
 
 extern "C" {
-
-#ifndef VL_BF16
-const char* vl_version(void) { return "vitlora-hip 0.3 (gfx950; fp16 / bf16 operands or fp32)"; }
-#endif
-#ifndef VL_BF16
-const char* vl_last_error(void) { return g_err.c_str(); }
-#endif
 
 int vl_create(const vl_config* cfg, vl_model** out) {
     if (!cfg || !out) return fail(VL_ERR_ARG, "null argument");
@@ -1025,15 +977,6 @@ int vl_set_normalization(vl_model* m, const float mean[3], const float stdv[3]) 
     return VL_OK;
 }
 
-#ifndef VL_BF16
-int vl_channel_affine(float* dst, const float* src, const float scale[3], const float shift[3], int batch, int64_t hw,
-                      void* stream) {
-    if (!dst || !src || !scale || !shift || batch <= 0 || hw <= 0) return fail(VL_ERR_ARG, "bad argument");
-    k_channel_affine(dst, src, scale, shift, batch, hw, (hipStream_t)stream);
-    return VL_OK;
-}
-#endif
-
 int vl_set_dropout_seed(vl_model* m, uint64_t seed) {
     if (!m) return fail(VL_ERR_ARG, "null model");
     m->drop_base = seed; m->drop_calls = 0;
@@ -1059,69 +1002,6 @@ int vl_backward_lora(vl_model* m, float* flat_grad_out, void* stream) {
     if (!m || !flat_grad_out) return fail(VL_ERR_ARG, "null argument");
     return backward_api(m, nullptr, flat_grad_out, (hipStream_t)stream);
 }
-
-// ---- handle-less utilities (the attacks: vit_attacks.hip) ------------------------------------
-#ifndef VL_BF16
-int vl_adam_step(float* param, const float* grad, float* m1, float* m2, float lr, float b1, float b2, float eps, int t,
-                 int64_t n, void* stream) {
-    if (!param || !grad || !m1 || !m2 || n <= 0 || t <= 0) return fail(VL_ERR_ARG, "bad argument");
-    int* err = nullptr;
-    for (const VlFlatRecord& mm : g_models)      // optimizer.step() on a model's flat parameters: its operands are stale now
-        if (param < mm.flat + mm.flat_n && param + n > mm.flat) { *mm.dirty = 1; err = *mm.err_flag; }
-    k_adam(param, grad, m1, m2, lr, b1, b2, eps, t, n, (hipStream_t)stream, err);
-    return VL_OK;
-}
-#endif
-
-#ifndef VL_BF16
-int vl_quantize_u8(const float* images, uint8_t* out_hwc, int batch, int channels, int height, int width, void* stream) {
-    if (!images || !out_hwc) return fail(VL_ERR_ARG, "null argument");
-    k_quantize(images, out_hwc, batch, channels, height, width, (hipStream_t)stream);
-    return VL_OK;
-}
-#endif
-
-// ---- adversarial patch (patch_attack.py: ART AdversarialPatchPyTorch) ------------------------------------
-#ifndef VL_BF16
-static int patch_args_ok(int batch, int image_size, int patch_size, int patch_type) {
-    if (batch <= 0 || image_size <= 0 || patch_size <= 0 || patch_size > 64 || patch_size > image_size)
-        return fail(VL_ERR_UNSUPPORTED, "patch_size must be in [1, min(64, image_size)]");
-    if (patch_type != 0 && patch_type != 1) return fail(VL_ERR_ARG, "patch_type: 0 = square, 1 = circle");
-    return VL_OK;
-}
-int vl_patch_apply_persp(const float* images, const float* patch, const float* inv_affine, const float* persp, int batch,
-                         int image_size, int patch_size, int patch_type, float* out, void* stream) {
-    if (!images || !patch || !inv_affine || !out || out == images) return fail(VL_ERR_ARG, "bad argument");
-    if (int rc = patch_args_ok(batch, image_size, patch_size, patch_type)) return rc;
-    k_patch_overlay(images, patch, inv_affine, persp, out, batch, image_size, patch_size, patch_type, (hipStream_t)stream);
-    if (!capturing((hipStream_t)stream)) return check_launch("vl_patch_apply");
-    return VL_OK;
-}
-int vl_patch_apply(const float* images, const float* patch, const float* inv_affine, int batch, int image_size, int patch_size,
-                   int patch_type, float* out, void* stream) {
-    return vl_patch_apply_persp(images, patch, inv_affine, nullptr, batch, image_size, patch_size, patch_type, out, stream);
-}
-int vl_patch_grad_persp(const float* grad_out, const float* inv_affine, const float* persp, int batch, int image_size,
-                        int patch_size, int patch_type, float* patch_grad, void* stream) {
-    if (!grad_out || !inv_affine || !patch_grad) return fail(VL_ERR_ARG, "bad argument");
-    if (int rc = patch_args_ok(batch, image_size, patch_size, patch_type)) return rc;
-    k_patch_overlay_bwd(grad_out, inv_affine, persp, patch_grad, batch, image_size, patch_size, patch_type, (hipStream_t)stream);
-    if (!capturing((hipStream_t)stream)) return check_launch("vl_patch_grad");
-    return VL_OK;
-}
-int vl_patch_grad(const float* grad_out, const float* inv_affine, int batch, int image_size, int patch_size, int patch_type,
-                  float* patch_grad, void* stream) {
-    return vl_patch_grad_persp(grad_out, inv_affine, nullptr, batch, image_size, patch_size, patch_type, patch_grad, stream);
-}
-#endif
-
-#ifndef VL_BF16
-int vl_clamp(float* x, float lo, float hi, int64_t n, void* stream) {
-    if (!x || n <= 0 || !(lo <= hi)) return fail(VL_ERR_ARG, "bad argument");
-    k_clamp(x, lo, hi, n, (hipStream_t)stream);
-    return VL_OK;
-}
-#endif
 
 // ---- GEMM micro-benchmark (tools/gemm_sweep.py): random h16 operands, HIP-event timing -----
 #ifndef VL_BF16
@@ -1459,56 +1339,9 @@ int vl_debug_set_option(vl_model* m, const char* name, int value) {
     return VL_OK;
 }
 
-#ifndef VL_BF16
+#ifndef VL_BF16      // (as vl_bench_gemm / vl_check_gemm: no handle, but they drive this build's GEMM kernels; the fp16 build exports them)
 int vl_debug_set_gemm_pp(int mode) { const int old = gemm_pp_mode(); gemm_pp_set_mode(mode); return old; }
-#endif
-#ifndef VL_BF16
 int vl_debug_set_gemm_stream(int mode) { return gemm_stream_set_mode(mode); }
-#endif
-
-// ---- profiling -------------------------------------------------------------------------------
-#ifndef VL_BF16
-int vl_profile_begin(void) {
-    if (g_prof) return fail(VL_ERR_STATE, "profile already active");
-    g_prof = new Profiler();
-    return VL_OK;
-}
-#endif
-
-// Synchronises the device, aggregates per kernel name and writes one JSON object:
-// {"name": {"n": launches, "ms": total_ms, "flops": total, "bytes": total, "exec_flops": total}, ...}
-// flops / bytes are ALGORITHMIC; exec_flops are the FLOPs the launches issue to the matrix pipes (padded rows,
-// padded attention tiles, the whole LoRA K tile) -- bench.py's roofline.path.executed_frac
-#ifndef VL_BF16
-int vl_profile_report(char* buf, size_t cap) {
-    if (!g_prof) return fail(VL_ERR_STATE, "profile not active");
-    Profiler* p = g_prof;
-    g_prof = nullptr;
-    if (hipDeviceSynchronize() != hipSuccess) { delete p; return fail(VL_ERR_HIP, "hipDeviceSynchronize failed"); }
-    struct Agg { std::string name; int n; double ms, flops, bytes, exec; };
-    std::vector<Agg> agg;
-    for (ProfRecord& r : p->recs) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, r.e0, r.e1);
-        (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1);
-        Agg* a = nullptr;
-        for (Agg& x : agg) if (x.name == r.name) { a = &x; break; }
-        if (!a) { agg.push_back({r.name, 0, 0, 0, 0, 0}); a = &agg.back(); }
-        a->n++; a->ms += ms; a->flops += r.flops; a->bytes += r.bytes; a->exec += r.exec_flops;
-    }
-    delete p;
-    std::string out = "{";
-    for (size_t i = 0; i < agg.size(); ++i) {
-        char line[320];
-        snprintf(line, sizeof line, "%s\"%s\": {\"n\": %d, \"ms\": %.6f, \"flops\": %.6e, \"bytes\": %.6e, \"exec_flops\": %.6e}",
-                 i ? ", " : "", agg[i].name.c_str(), agg[i].n, agg[i].ms, agg[i].flops, agg[i].bytes, agg[i].exec);
-        out += line;
-    }
-    out += "}";
-    if (!buf || cap < out.size() + 1) return fail(VL_ERR_ARG, "buffer too small (%zu needed)", out.size() + 1);
-    memcpy(buf, out.c_str(), out.size() + 1);
-    return VL_OK;
-}
 #endif
 
 int vl_debug_counter(vl_model* m, const char* what, int64_t* value) {

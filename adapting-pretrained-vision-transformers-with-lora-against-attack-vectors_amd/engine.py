@@ -628,7 +628,7 @@ class Engine:
 def apgd_schedule(n_iter: int):
     """Checkpoints of Auto-PGD for n_iter iterations as (i, k) pairs: iteration i ends a window of k iterations
     (k0 = max(int(.22 N), 1), shrinking by max(int(.03 N), 1) down to max(int(.06 N), 1)).  The library builds the same table on
-    the device (csrc/elementwise.hip: apgd_sched_kernel)."""
+    the device (csrc/once_kernels.hip: apgd_sched_kernel)."""
     n = int(n_iter)
     k, k_min, dec = max(int(0.22 * n), 1), max(int(0.06 * n), 1), max(int(0.03 * n), 1)
     out, cnt = [], 0

@@ -32,6 +32,26 @@ def test_library_exports_every_header_symbol():
     assert set(lib_mod.SIGNATURES) - set(names) <= {"vl_bench_gemm"}   # binding has nothing the header lacks
 
 
+ONCE_COMPILED_KERNELS = (
+    "adam_kernel", "apgd_rand_init_kernel", "apgd_sched_kernel", "apgd_start_kernel", "apgd_step_kernel", "apgd_targets_kernel",
+    "apgd_track_kernel", "apgdt_fold_kernel", "ce_loss_kernel", "ce_reduce_kernel", "channel_affine_kernel",
+    "dlr_targeted_loss_kernel", "pgd_init_kernel", "pgd_step_kernel", "quantize_kernel", "square_init_kernel",
+    "square_sched_kernel", "square_step_kernel", "square_track_kernel", "zero_kernel",
+    "grad_scale_kernel", "classifier_grad_kernel", "dropout_mask_kernel", "merge_f32_kernel")
+
+
+def test_precision_independent_kernels_are_compiled_once():
+    """csrc/once_kernels.hip: the kernels that never touch a 16-bit operand exist ONCE in the library, not once per build of
+    the 16-bit path (fp16 / bf16 operands: csrc/common.h).  Each kernel's host-side launch stub is one symbol of the .so."""
+    import shutil
+    if shutil.which("nm") is None:
+        pytest.skip("nm not on PATH")
+    out = subprocess.run(["nm", pkg().LIB_PATH], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    counts = {k: sum(1 for line in out.stdout.splitlines() if f"__device_stub__{k}E" in line) for k in ONCE_COMPILED_KERNELS}
+    assert all(v == 1 for v in counts.values()), {k: v for k, v in counts.items() if v != 1}
+
+
 def test_engine_refuses_to_run_without_gpu():
     if torch.cuda.is_available():
         pytest.skip("GPU present")

@@ -22,7 +22,7 @@ pos = [g for g in gaps if g > 0]
 print(f"kernels {len(seg)}  wall {wall/1e6:.3f} ms  busy {busy/1e6:.3f} ms  ({busy/wall:.3f})  mean gap {sum(pos)/max(1,len(pos))/1e3:.2f} us over {len(pos)} gaps, overlapping pairs {len(gaps)-len(pos)}")
 by = collections.defaultdict(lambda: [0, 0])
 for s, e, k in seg:
-    k = k.replace("(anonymous namespace)::", "").replace("void ", "").replace("vl_f16::", "").split("(")[0][-60:]
+    k = k.replace("(anonymous namespace)::", "").replace("void ", "").replace("vl_f16::", "").replace("vl_once::", "").split("(")[0][-60:]
     by[k][0] += 1; by[k][1] += e - s
 for k, (c, t) in sorted(by.items(), key=lambda x: -x[1][1])[:25]:
     print(f"  {t/1e6:8.3f} ms {c:6d} x {t/c/1e3:7.1f} us  {k}")

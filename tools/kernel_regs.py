@@ -16,7 +16,7 @@ for line in out.splitlines():
     if m:
         name = m.group(1)
         # light demangling of the template arguments (c++filt here predates the _Float16 mangling)
-        t = re.match(r"_ZN12_GLOBAL__N_1\d+([A-Za-z0-9_]+?_kernel)(I.*?E)?Ev", name)
+        t = re.match(r"_ZN(?:\d+vl_(?:b?f16|once))?12_GLOBAL__N_1\d+([A-Za-z0-9_]+?_kernel)(I.*?E)?E[Pv]", name)
         if t:
             args = re.findall(r"L[ib](\d+)E", t.group(2) or "")
             name = t.group(1) + ("<" + ", ".join(args) + ">" if args else "")

@@ -22,8 +22,8 @@ for name, counter, value, disp in c.execute("select kernel_name, counter_name, v
     k = name.replace("(anonymous namespace)::", "").replace("void ", "")
     k = re.sub(r"\(.*$", "", k)
     k = re.sub(r"^_ZN12_GLOBAL__N_1\d+", "", k)
-    k = re.sub(r"^_ZN\d+vl_b?f16\d+_GLOBAL__N_1\d+", "", k)      # kernels of the two 16-bit builds (namespaces vl_f16 / vl_bf16)
-    k = k.replace("vl_f16::", "").replace("vl_bf16::", "")
+    k = re.sub(r"^_ZN\d+vl_(?:b?f16|once)\d+_GLOBAL__N_1\d+", "", k)      # the two 16-bit builds (vl_f16 / vl_bf16), the once-compiled kernels (vl_once)
+    k = k.replace("vl_f16::", "").replace("vl_bf16::", "").replace("vl_once::", "")
     k = re.sub(r"ILi(\d+)ELi(\d+)ELb(\d)EEEv.*$", r"<\1, \2, \3>", k)          # <int, int, bool>
     k = re.sub(r"ILi(\d+)EEEv.*$", r"<\1>", k)
     k = re.sub(r"ILi(\d+)ELi(\d+)EE.*$", r"<\1, \2>", k)

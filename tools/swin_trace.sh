@@ -17,7 +17,7 @@ last_init = max(i for i, r in enumerate(rows) if "pgd_init" in r[2])
 seg = [r for r in rows[last_init + 1:] if "copyBuffer" not in r[2] and "fillBuffer" not in r[2]]
 by = collections.defaultdict(lambda: [0, 0])
 for s, e, k in seg:
-    k = k.replace("(anonymous namespace)::", "").replace("void ", "").replace("vl_f16::", "").split("(")[0][-70:]
+    k = k.replace("(anonymous namespace)::", "").replace("void ", "").replace("vl_f16::", "").replace("vl_once::", "").split("(")[0][-70:]
     by[k][0] += 1; by[k][1] += e - s
 tot = sum(t for c, t in by.values())
 print(open(out + "/run.txt").read().strip())
